@@ -10,6 +10,14 @@ downmix (lib.rs:42) -> reflect framing + Hann/n_fft (lib.rs:367-440) -> real FFT
 (stft3_kernel). Files shard across ranks by LPT (thesia.shard) with no
 data-path collective ("weak" scaling: per-GPU work is fixed).
 
+A plain run sets the shard up, warms up, times the K steps and prints the result line (value =
+frames per second of the timed steps, ms_per_step = one timed step). `--full` adds everything
+reported beside it, each from runs of its own after the timed steps: the kernel-time rooflines
+and copy ceilings, the bit-exact kernel, the CPU baseline, the C1 line and the PCIe-inclusive
+sample. `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy
+(float32; a fixed seeded sample where the output is larger than 48 MB); the inputs are seeded,
+so two builds can be compared output for output.
+
 Launch: `python bench.py [--gpus N --steps K --warmup W]`. With --gpus N > 1 and no
 WORLD_SIZE in the environment this process is only a launcher: it spawns N worker processes
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, one per GPU) before anything touches a GPU,
@@ -101,7 +109,28 @@ def parse():
     p.add_argument("--selftest", action="store_true",
                    help="launcher / reduction plumbing only: no GPU, no thesia (CPU tests)")
     p.add_argument("--selftest-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure everything reported beside the headline: the "
+                        "kernel-time rooflines and copy ceilings, the bit-exact / tolerance path beside the "
+                        "line's, the CPU baseline, the C1 line, the PCIe-inclusive sample (c4 / c3), the "
+                        "host-copy step and the display roofline (c5); the --no-* options drop single sections "
+                        "of it. Off by default: a plain run sets up, "
+                        "warms up, times --steps steps and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step left in its output buffers as "
+                        "DIR/<name>.npy (float32; a fixed, seeded sample of blocks where the output is larger "
+                        "than the 48 MB budget; <name>_rank<r>.npy with more than one rank)")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:
+        needs = [o for o, v in (("--row-stores", a.row_stores),
+                                ("--spec-policies", a.spec_policies), ("--render-paths", a.render_paths),
+                                ("--max-blocks", a.max_blocks if a.workload == "c5" else "")) if v]
+        if needs:
+            p.error(f"{', '.join(needs)}: reported inside the roofline sections, which need --full")
+    if a.dump_outputs and (a.workload == "viewer" or a.selftest):
+        p.error("--dump-outputs: the viewer workload and --selftest have no timed steps to dump")
     if a.win is None:
         a.win = a.n_fft
     if a.seconds is None:
@@ -205,6 +234,38 @@ def ranks_summary(reports: list, frames_key: str = "frames") -> dict:
     return {"n_devices": len(devices), "devices": devices,
             "per_rank_frames": [int(r[frames_key]) for r in reports],
             "total_frames": int(sum(r[frames_key] for r in reports))}
+
+
+DUMP_BUDGET = 48 << 20  # bytes of .npy data per run (all ranks, all arrays)
+DUMP_BLOCK = 1 << 16  # elements per sampled block
+
+
+def sample_device(buf, dtype, n_elems: int, budget_bytes: int):
+    """`buf`'s first n_elems elements of `dtype` as float32, whole if that fits budget_bytes,
+    else a fixed sample of DUMP_BLOCK-element blocks: the first, the last (partial) one and a
+    seeded choice of the others, in buffer order. The choice depends on n_elems and the budget
+    only, so two runs with the same arguments sample the same elements."""
+    import numpy as np
+    if n_elems * 4 <= budget_bytes:
+        return buf.read(dtype, n_elems).astype(np.float32)
+    n_blocks = (n_elems + DUMP_BLOCK - 1) // DUMP_BLOCK
+    k = max(2, budget_bytes // (4 * DUMP_BLOCK))
+    inner = np.random.default_rng(0).choice(n_blocks - 2, k - 2, replace=False) + 1
+    parts = [buf.read(dtype, min(DUMP_BLOCK, n_elems - int(j) * DUMP_BLOCK), int(j) * DUMP_BLOCK)
+             for j in [0, *sorted(inner.tolist()), n_blocks - 1]]
+    return np.concatenate(parts).astype(np.float32)
+
+
+def dump_outputs(args, ws: int, rank: int, buffers: dict) -> None:
+    """--dump-outputs: every rank writes its own arrays. buffers: name -> (DeviceBuffer, dtype,
+    element count), or a small host array (written whole, as float64); the budget is split evenly
+    over ranks and arrays."""
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_BUDGET // (ws * max(1, len(buffers)))
+    for name, v in buffers.items():
+        a = v.astype(np.float64) if isinstance(v, np.ndarray) else sample_device(*v, share)
+        np.save(os.path.join(args.dump_outputs, name + (f"_rank{rank}" if ws > 1 else "") + ".npy"), a)
 
 
 def cpu_info() -> dict:
@@ -511,6 +572,28 @@ def main_selftest(args, ws, rank, pg):
                           "pids": [r["pid"] for r in reps]}), flush=True)
 
 
+def c5_result(args, ws, summ, dt, total, n_local, p, main_k) -> dict:
+    """The C5 result line as the timed steps alone give it (--full adds the sections beside it)."""
+    return {
+        "metric": METRIC,
+        "value": summ["total_frames"] / dt, "unit": "frames/s", "n_gpus": summ["n_devices"], "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic (int16 chirp + noise, seeded per track), resident in HBM",
+        "config": {"workload": f"C5: {total} mixed-rate tracks (8-48 kHz) x {args.seconds:g} s, "
+                               f"n_fft 256-2048 per track, hop n_fft/4, amp dB + global range + "
+                               f"grey + Lanczos3 + colormap RGB at 100 px/s x 500 px",
+                   "ranks": ws, "devices": summ["devices"], "per_rank_frames": summ["per_rank_frames"],
+                   "tracks_per_gpu": n_local, "images_per_s": total / dt,
+                   "spectrogram_batches": len(p.groups), "display_groups": p._n_disp,
+                   "frames_per_gpu": p.total_frames,
+                   "spectrogram_path": (f"kernel {main_k}: reference-order streaming kernels (stftq at n_fft "
+                                        f"256-1024, stftr at 2048), RGB bytes equal to the oracle pipeline's"
+                                        if main_k == 7 else f"kernel {main_k} (0 = automatic, tolerance)"),
+                   "parallelism": f"file-sharded x{ws} (LPT), one all_reduce of 3 scalars"},
+    }
+
+
 def main_c5(args, ws, rank, pg, device):
     """C5 (BASELINE.json configs[4]): mixed-rate tracks with per-track n_fft, amp dB, global
     range exchange, grey + Lanczos3 + colormap RGB for every track (thesia.pipeline). One step =
@@ -577,6 +660,17 @@ def main_c5(args, ws, rank, pg, device):
     # reported beside it (tolerance_path). --kernel K / --no-exact measure that path instead.
     main_k = 7 if (args.kernel == 0 and not args.no_exact) else args.kernel
     dt = timed_steps(main_k, args.warmup, args.steps)
+    if args.dump_outputs:  # the last timed step's images (the u8 RGB of every track, call order) and ranges
+        import numpy as np
+        dump_outputs(args, ws, rank, {"rgb": (p._rgb, np.uint8, p._rgb_total),
+                                      "ranges_db": np.stack(p._range_arrays())})
+    if not args.full:
+        reps = gather_reports(pg, {"device": device, "frames": p.total_frames, "tracks": len(tracks)})
+        summ = ranks_summary(reps)
+        if rank == 0:
+            print(json.dumps(c5_result(args, ws, summ, dt, total, len(tracks), p, main_k)), flush=True)
+        p.close()
+        return
     step(want_rgb=True)  # untimed: pins the host readback buffers once (hipHostRegister)
     engine.synchronize()
     t0 = time.perf_counter()
@@ -672,24 +766,9 @@ def main_c5(args, ws, rank, pg, device):
     reps = gather_reports(pg, {"device": device, "frames": p.total_frames, "tracks": len(tracks)})
     summ = ranks_summary(reps)
     if rank == 0:
-        print(json.dumps({
-            "metric": METRIC,
-            "value": summ["total_frames"] / dt, "unit": "frames/s", "n_gpus": summ["n_devices"], "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic (int16 chirp + noise, seeded per track), resident in HBM",
-            "config": {"workload": f"C5: {total} mixed-rate tracks (8-48 kHz) x {args.seconds:g} s, "
-                                   f"n_fft 256-2048 per track, hop n_fft/4, amp dB + global range + "
-                                   f"grey + Lanczos3 + colormap RGB at 100 px/s x 500 px",
-                       "ranks": ws, "devices": summ["devices"], "per_rank_frames": summ["per_rank_frames"],
-                       "tracks_per_gpu": len(tracks), "images_per_s": total / dt,
-                       "spectrogram_batches": len(p.groups), "display_groups": p._n_disp,
-                       "frames_per_gpu": p.total_frames,
-                       "spectrogram_path": (f"kernel {main_k}: reference-order streaming kernels (stftq at n_fft "
-                                            f"256-1024, stftr at 2048), RGB bytes equal to the oracle pipeline's"
-                                            if main_k == 7 else f"kernel {main_k} (0 = automatic, tolerance)"),
-                       "ms_per_step_with_rgb_copied_to_host": dt_host * 1e3,
-                       "parallelism": f"file-sharded x{ws} (LPT), one all_reduce of 3 scalars"},
+        result = c5_result(args, ws, summ, dt, total, len(tracks), p, main_k)
+        result["config"]["ms_per_step_with_rgb_copied_to_host"] = dt_host * 1e3
+        result.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                          "kernel": "spectrogram launches of all geometry groups",
@@ -708,7 +787,8 @@ def main_c5(args, ws, rank, pg, device):
             "tolerance_path": tol,
             "roofline_display": disp,
             "roofline_display_valu_issue": disp_ic,
-        }), flush=True)
+        })
+        print(json.dumps(result), flush=True)
     p.close()
 
 
@@ -975,6 +1055,9 @@ def main_worker(args):
     t1 = time.perf_counter()
     dt = max_over_ranks(pg, (t1 - t0) / args.steps)
 
+    if args.dump_outputs:  # the rows the last timed step left ([frames, row_bins]; complex rows as re, im pairs)
+        dump_outputs(args, ws, rank, {args.output: (dout, np.float32, dout.nbytes // 4)})
+
     if args.variants:
         vs = [int(v) for v in args.variants.split(",")]
         res = {v: [] for v in vs}
@@ -1027,11 +1110,12 @@ def main_worker(args):
             print(json.dumps({"mel_paths_ms": {str(q): {"median": float(np.median(t)), "min": float(min(t))}
                                                for q, t in res.items()}}), flush=True)
 
-    # kernel duration from HIP events on the launch stream (roofline numerator / denominator)
-    kms = batch.run_timed(max(args.steps, 5)) / max(args.steps, 5)
-    kms = max_over_ranks(pg, kms)
-    abytes = algorithmic_bytes(args, n_local, n_samples, frames, plan.row_bins)
-    achieved = abytes / (kms * 1e-3) / 1e9
+    if args.full:
+        # kernel duration from HIP events on the launch stream (roofline numerator / denominator)
+        kms = batch.run_timed(max(args.steps, 5)) / max(args.steps, 5)
+        kms = max_over_ranks(pg, kms)
+        abytes = algorithmic_bytes(args, n_local, n_samples, frames, plan.row_bins)
+        achieved = abytes / (kms * 1e-3) / 1e9
 
     reps = gather_reports(pg, {"device": device, "frames": frames, "tracks": n_local})
     summ = ranks_summary(reps)
@@ -1063,7 +1147,9 @@ def main_worker(args):
             "parallelism": f"file-sharded x{ws}, no collective",
         },
     }
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(result), flush=True)
+    elif rank == 0:
         rec = profile_record(workload_params(args, batch.kernel))
         result["roofline"] = {
             "bound": "hbm",

@@ -9,7 +9,7 @@ REPO="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$REPO/gpurun_out"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BARGS=${BENCH_ARGS:---steps 10 --warmup 2 --no-cpu-baseline}
+BARGS=${BENCH_ARGS:---full --steps 10 --warmup 2 --no-cpu-baseline}
 crash() { case "$1" in 0|1) return 1;; *) return 0;; esac; }
 if [ "${SKIP_KT:-0}" != 1 ]; then
   rocprofv3 -L > "$OUT/rocprof_counters.txt" 2>&1 || true

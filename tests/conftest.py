@@ -8,8 +8,6 @@ sys.path.insert(0, os.path.join(ROOT, "multi-spectrogram-viewer_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 
-REFERENCE = "/root/reference"
-
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (runs the HIP kernels)")

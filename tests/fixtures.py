@@ -16,7 +16,7 @@ def c1_substitute() -> np.ndarray:
     clipped to int16, cut to the 2 113 529 samples audio.rs:66 expects. Returns int16 [n]."""
     from scipy.signal import resample_poly
 
-    x = np.load(os.path.join(GOLDEN, "samples_full.npz"))["pcm_24k"].astype(np.float64)
+    x = sample_full("24k")[0].astype(np.float64)
     y = np.clip(np.round(resample_poly(x, 2, 1)), -32768, 32767).astype(np.int16)
     assert y.shape[0] >= C1_LEN
     return y[:C1_LEN]
@@ -30,7 +30,15 @@ def s16_to_f32(x: np.ndarray) -> np.ndarray:
 SAMPLE_TAGS = ["8k", "16k", "22k05", "24k", "44k1"]
 
 
+def sample_full(tag: str):
+    """One committed sample WAV whole, (int16 pcm, sr): the parts tests/golden/samples_full/
+    <tag>.NN.npz (350 000 samples each, make_golden.py) joined in order."""
+    d = os.path.join(GOLDEN, "samples_full")
+    parts = [np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.startswith(tag + ".")]
+    assert parts, tag
+    return np.concatenate([z["pcm"] for z in parts]), int(parts[0]["sr"])
+
+
 def samples_full():
     """The five committed sample WAVs whole: [(int16 pcm, sr)] in rate order."""
-    z = np.load(os.path.join(GOLDEN, "samples_full.npz"))
-    return [(z[f"pcm_{t}"], int(z[f"sr_{t}"])) for t in SAMPLE_TAGS]
+    return [sample_full(t) for t in SAMPLE_TAGS]

@@ -13,8 +13,8 @@ reference is mounted at /root/reference; the GPU box never reads the reference).
      audio.rs:44-70    the missing 48 kHz sample's expected header (documentation only)
 2. samples_excerpt.npz -- int16 excerpts (first 1.5 s) of the reference's sample WAVs
    (data fixtures from /root/reference/samples), keyed by sample rate, plus full lengths.
-3. samples_full.npz -- the five sample WAVs whole (int16, 44.03 s each): config C2 at the size
-   BASELINE.json names, and (the 24 kHz one, 1 056 765 samples) the source of the 48 kHz
+3. samples_full/<tag>.NN.npz -- the five sample WAVs whole (int16, 44.03 s each), in parts of
+   350 000 samples so that no committed file passes 1 MiB: config C2 at the size BASELINE.json names, and (the 24 kHz one, 1 056 765 samples) the source of the 48 kHz
    substitute for the missing samples/sample_48k.wav (config C1, SURVEY.md §8d;
    tests/fixtures.py c1_substitute).
 """
@@ -26,6 +26,7 @@ import numpy as np
 
 REF = "/root/reference"
 HERE = os.path.dirname(os.path.abspath(__file__))
+FULL_PART = 350000  # samples per samples_full/ part
 
 
 def kats():
@@ -92,5 +93,11 @@ if __name__ == "__main__":
     with open(os.path.join(HERE, "kats.json"), "w") as f:
         json.dump(kats(), f, indent=1)
     np.savez_compressed(os.path.join(HERE, "samples_excerpt.npz"), **samples())
-    np.savez_compressed(os.path.join(HERE, "samples_full.npz"), **samples_full())
-    print("wrote kats.json, samples_excerpt.npz, samples_full.npz")
+    full = samples_full()
+    os.makedirs(os.path.join(HERE, "samples_full"), exist_ok=True)
+    for tag in ["8k", "16k", "22k05", "24k", "44k1"]:
+        pcm = full[f"pcm_{tag}"]
+        for k, i in enumerate(range(0, len(pcm), FULL_PART)):
+            np.savez_compressed(os.path.join(HERE, "samples_full", f"{tag}.{k:02d}.npz"),
+                                pcm=pcm[i:i + FULL_PART], sr=full[f"sr_{tag}"])
+    print("wrote kats.json, samples_excerpt.npz, samples_full/")

@@ -1,7 +1,7 @@
 """WAV parsing with hound 3.4 semantics (audio.rs:9-37) on the host: thesia.open_audio_file
 against the committed synthetic fixtures (tests/golden/make_wav_fixtures.py: 8/16/24/32-bit
 integer, f32, stereo / 3- / 6-channel, WAVE_FORMAT_EXTENSIBLE, an odd-length chunk before the
-data) and, when the reference checkout is present, its own sample WAVs."""
+data) and the reference's own sample recordings, rewritten from the committed PCM."""
 import os
 
 import numpy as np
@@ -42,17 +42,26 @@ def test_open_audio_file_errors(tmp_path):
     assert e.value.code == ERR_UNSUPPORTED  # the rodio fallback is out of scope
 
 
-REF_SAMPLES = "/root/reference/samples"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_SAMPLES), reason="reference checkout not present")
 @pytest.mark.parametrize("tag", ["8k", "16k", "22k05", "24k", "44k1"])
-def test_reference_sample_wavs(tag):
-    # the reference's own 16-bit sample files (its open_audio_works KAT names samples/sample.wav,
-    # which the checkout does not hold): length, rate and the committed 1.5 s int16 excerpt
+def test_reference_sample_wavs(tag, tmp_path):
+    # the reference's own 16-bit mono sample recordings (its open_audio_works KAT names
+    # samples/sample.wav, which it does not hold), written out again as the plain 44-byte-header
+    # WAV files they are from the committed PCM (tests/golden/samples_full/): length, rate, the
+    # committed 1.5 s int16 excerpt and every sample
+    import wave
+
+    import fixtures
+    pcm, rate = fixtures.sample_full(tag)
+    path = str(tmp_path / f"sample_{tag}.wav")
+    with wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(rate)
+        w.writeframes(pcm.astype("<i2").tobytes())
     z = np.load(os.path.join(HERE, "golden", "samples_excerpt.npz"))
-    wav, sr = thesia.open_audio_file(os.path.join(REF_SAMPLES, f"sample_{tag}.wav"))
+    wav, sr = thesia.open_audio_file(path)
     assert sr == int(z[f"sr_{tag}"]) and wav.shape == (1, int(z[f"len_{tag}"]))
     ex = z[f"pcm_{tag}"]
     want = (ex.astype(np.float32) / np.float32(32768.0)).astype(np.float32)
     assert np.array_equal(wav[0, :ex.size], want)
+    assert np.array_equal(wav[0], fixtures.s16_to_f32(pcm))
