@@ -1376,7 +1376,7 @@ int launch_render_batch2(const float* spec, uint32_t bins, float max, float min,
     if (v_fpl == 4 || v_fpl == 2) {
         // K4+K5v wide: every band's grey rows fit the tile (host: v_rows <= the FPL's cap)
         const int lds1 = grey_vert_wide_lds_bytes(v_fpl, v_band, v_rows, kv);
-        if (lds1 > 163840) return -2;
+        if (lds1 > kLdsMax) return -2;
         const void* kern = v_fpl == 4 ? reinterpret_cast<const void*>(grey_vert_wide_kernel<4>)
                                       : reinterpret_cast<const void*>(grey_vert_wide_kernel<2>);
         if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds1) != hipSuccess) return -1;
@@ -1390,7 +1390,7 @@ int launch_render_batch2(const float* spec, uint32_t bins, float max, float min,
         // does not fit reads HBM directly)
         const int tile_cap = v_rows < 256 ? v_rows : 256;
         const int lds1 = ((((int)v_band + 3) & ~3) + ((tile_cap * 65 + 3) & ~3) + (int)v_band * kv) * 4;
-        if (lds1 > 163840) return -2;
+        if (lds1 > kLdsMax) return -2;
         const void* vk = reinterpret_cast<const void*>(grey_vert_kernel);
         if (hipFuncSetAttribute(vk, hipFuncAttributeMaxDynamicSharedMemorySize, lds1) != hipSuccess) return -1;
         dim3 g1((T_max + 63) / 64, (nh + v_band - 1) / v_band, n);

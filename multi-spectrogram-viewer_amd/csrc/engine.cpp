@@ -306,7 +306,7 @@ hipStream_t default_stream() {
 // plans
 // ------------------------------------------------------------------------------------
 size_t Plan::row_bins() const {
-    if (out_kind == OUT_MEL || out_kind == OUT_MEL_AMP_DB) return n_mels;
+    if (is_mel_kind(out_kind)) return n_mels;
     return NC + 1;
 }
 
@@ -854,6 +854,65 @@ Batch::~Batch() {
     if (ev1) (void)hipEventDestroy(ev1);
 }
 
+// Kernel selection: one row per THESIA_BATCH_OPT_KERNEL value. runs: the kernel has an instance
+// for the launch's geometry / format / channels, the tables it needs are there and its LDS fits;
+// folds_range: its epilogue accumulates the per-track range of these rows (else one pass over the
+// rows follows the launch); fallback: the row that takes over when the launch returns -2.
+static bool never(const StftLaunch&) { return false; }
+static bool runs_stft3(const StftLaunch& a) {
+    // (stft2's sizes; the mel weights must fit LDS, else stft2)
+    return stft2_supports(a.n_fft) && stft3_supports(a) && stft3_lds_bytes(a) <= kLdsMax;
+}
+// (the viewer geometry runs stft5 for the mel and linear kinds only: complex rows stay on stft3)
+static bool stft5_geometry(const StftLaunch& a) { return runs_stft3(a) && stft5_supports(a); }
+struct KernelRow {
+    int id;
+    const char* name;
+    bool (*runs)(const StftLaunch&);
+    int (*launch)(const StftLaunch&, hipStream_t);
+    bool (*folds_range)(const StftLaunch&);
+    int fallback;  // 0: none
+};
+static const KernelRow kKernels[] = {
+    {1, "stft", [](const StftLaunch&) { return true; }, launch_stft, never, 0},
+    {2, "stft2", [](const StftLaunch& a) { return stft2_supports(a.n_fft); }, launch_stft2, never, 1},
+    // stft3 folds the range into its staged-row epilogue (linear kinds, the default row store)
+    {3, "stft3", runs_stft3, launch_stft3,
+     [](const StftLaunch& a) { return a.out_kind != OUT_COMPLEX && !is_mel_kind(a.out_kind) && a.row_alt == 0; }, 2},
+    {5, "stft5", [](const StftLaunch& a) { return stft5_geometry(a) && stft5_lds_bytes(a) <= kLdsMax; },
+     launch_stft5, never, 3},
+    // the reference-order streaming kernels: stftr at n_fft 2048 (mel kinds need its packed
+    // stream, 64 lanes per frame), stftq at n_fft 256 / 512 / 1024; amp dB rows fold their range
+    // into the epilogue (the RG instances)
+    {7, "stft7 (stftr / stftq)", [](const StftLaunch& a) { return stft7_supports(a) && stft7_lds_bytes(a) <= kLdsMax; },
+     launch_stft7, [](const StftLaunch& a) { return a.out_kind == OUT_AMP_DB; }, 0},
+    {9, "stftx", [](const StftLaunch& a) { return stftx_lds_bytes(a.n_fft, true) <= kLdsMax; }, launch_stftx, never, 0},
+};
+static const KernelRow* kernel_row(int id) {
+    for (const KernelRow& k : kKernels)
+        if (k.id == id) return &k;
+    return nullptr;
+}
+bool kernel_runs(const Batch& b, int id) { return id > 0 && id < 32 && (b.runs_mask >> id & 1u); }
+
+// automatic choice: stft5 for the mel kinds at n_fft 2048 and for linear rows without the
+// range option (measured faster there: stereo power dB 5.64 vs 6.22 ms in round 3; slower for
+// complex rows, 9.0 vs 6.98 ms, and stft3 folds the per-track range into its row epilogue;
+// DESIGN.md §6), stft3 for the other streaming geometries, then the 4-waves/SIMD kernel for
+// its sizes, else the general one
+// at the viewer geometry stft5 pays only on large batches: its per-block setup
+// (the packed mel stream, the rotation tables) against stft3's, measured at 48 kHz mel-128
+// (profiles/r04_viewer/batch_size_ab.txt): 3.0e6 frames 4.48 vs 4.76 ms, 3.0e5 0.576 vs
+// 0.570, 2.6e4 0.102 vs 0.077
+static constexpr uint64_t kView5MinFrames = 400000;
+int auto_kernel(const Batch& b) {
+    const bool mel = is_mel_kind(b.launch.out_kind);
+    const bool plain_lin = !mel && b.launch.out_kind != OUT_COMPLEX && !b.range;  // linear rows, no range
+    const bool k5 = kernel_runs(b, 5) && (mel || plain_lin) &&
+                    (canon_geometry(b.launch) || b.total_frames >= kView5MinFrames);
+    return k5 ? 5 : kernel_runs(b, 3) ? 3 : kernel_runs(b, 2) ? 2 : 1;
+}
+
 int batch_create(Plan* plan, const thesia_batch_desc& d, Batch** out) {
     *out = nullptr;
     if (!plan) return set_error(THESIA_ERR_INVALID_ARG, "null plan");
@@ -934,38 +993,22 @@ int batch_create(Plan* plan, const thesia_batch_desc& d, Batch** out) {
     L.mel_xo = plan->mel_xo.as<int>();
     L.out = d.d_output;
     b->apply_mel_path();
-    // kernel choice: the streaming kernel for its geometry, else the 4-waves/SIMD kernel for
-    // its sizes, else the general one (thesia_batch_set_option can force another one)
-    b->k3_ok = plan->use_v2 && stft3_supports((int)plan->n_fft, (int)plan->win, (int)plan->hop,
-                                              d.input_format, (int)d.channels) &&
-               stft3_lds_bytes(L) <= 163840;  // the mel weights must fit LDS (else stft2)
-    // (the viewer geometry runs stft5 for the mel and linear kinds only: complex rows stay on stft3)
-    const bool view5 = !(plan->win == plan->n_fft && plan->hop * 4 == plan->n_fft);
-    const bool k5_geo = b->k3_ok && stft5_supports((int)plan->n_fft, (int)plan->win, (int)plan->hop,
-                                                   d.input_format, (int)d.channels) &&
-                        !(view5 && L.out_kind == OUT_COMPLEX);
-    if (k5_geo && L.melp_chunks && stft5_lds_bytes(L) > 163840) {  // packed stream too big: rounds
-        b->mel_path = 1;
-        b->apply_mel_path();
-    }
-    b->k5_ok = k5_geo && stft5_lds_bytes(L) <= 163840;
-    // the reference-order streaming kernels (kernel 7): stftr at the canonical n_fft 2048
-    // geometry (mel kinds need its packed stream, 64 lanes per frame), stftq at n_fft 256 / 512 /
-    // 1024
-    if (plan->melr_best >= 0) {
+    if (plan->melr_best >= 0) {  // stftr's packed mel stream
         const Plan::Melp& m = plan->melr[plan->melr_best];
         L.melr_chunks = m.chunks;
         L.melr_steps = m.steps;
         L.melr_meta = m.meta.as<int4>();
         L.melr_wt = m.wt.as<float4>();
     }
-    const bool mel_kind = L.out_kind == OUT_MEL || L.out_kind == OUT_MEL_AMP_DB;
-    b->kr_ok = (stftr_supports((int)plan->n_fft, (int)plan->win, (int)plan->hop, d.input_format, (int)d.channels) &&
-                (!mel_kind || L.melr_chunks > 0) && stftr_lds_bytes(L) <= 163840) ||
-               (stftq_supports((int)plan->n_fft, (int)plan->win, (int)plan->hop, d.input_format, (int)d.channels) &&
-                stftq_lds_bytes(L) <= 163840);
-    b->k5_view = view5;
-    b->kernel = b->auto_kernel();
+    if (stft5_geometry(L) && L.melp_chunks && stft5_lds_bytes(L) > kLdsMax) {  // packed stream too big: rounds
+        b->mel_path = 1;
+        b->apply_mel_path();
+    }
+    // kernel choice: the streaming kernel for its geometry, else the 4-waves/SIMD kernel for
+    // its sizes, else the general one (thesia_batch_set_option can force another one)
+    for (const KernelRow& k : kKernels)
+        if (k.runs(L)) b->runs_mask |= 1u << k.id;
+    b->kernel = auto_kernel(*b);
     if (hipEventCreate(&b->ev0) != hipSuccess || hipEventCreate(&b->ev1) != hipSuccess) {
         delete b;
         return set_error(THESIA_ERR_DEVICE, "hipEventCreate failed");
@@ -993,13 +1036,8 @@ void Batch::apply_mel_path() {
 int batch_set_option(Batch* b, int option, int64_t value) {
     switch (option) {
         case THESIA_BATCH_OPT_KERNEL:
-            if (value == 0) b->kernel = b->auto_kernel();
-            else if (value == 1) b->kernel = 1;
-            else if (value == 2 && stft2_supports((int)b->plan->n_fft)) b->kernel = 2;
-            else if (value == 3 && b->k3_ok) b->kernel = 3;
-            else if (value == 5 && b->k5_ok) b->kernel = 5;
-            else if (value == 7 && b->kr_ok) b->kernel = 7;
-            else if (value == 9 && stftx_lds_bytes((int)b->plan->n_fft, true) <= 163840) b->kernel = 9;
+            if (value == 0) b->kernel = auto_kernel(*b);
+            else if (value > 0 && value < 32 && kernel_runs(*b, (int)value)) b->kernel = (int)value;
             else return set_error(THESIA_ERR_UNSUPPORTED, "kernel " + std::to_string(value) +
                                                              " does not run this batch's geometry");
             b->kernel_forced = value != 0;
@@ -1017,7 +1055,7 @@ int batch_set_option(Batch* b, int option, int64_t value) {
             if (value != 0 && b->launch.out_kind == OUT_COMPLEX)
                 return set_error(THESIA_ERR_INVALID_ARG, "ranges need real output rows");
             b->range = reinterpret_cast<int*>(value);
-            if (!b->kernel_forced) b->kernel = b->auto_kernel();  // the range decides stft3 vs stft5
+            if (!b->kernel_forced) b->kernel = auto_kernel(*b);  // the range decides stft3 vs stft5
             return THESIA_OK;
         case THESIA_BATCH_OPT_MEL_PATH: {
             if (value < 0 || value > 3) return set_error(THESIA_ERR_INVALID_ARG, "mel_path must be 0..3");
@@ -1026,7 +1064,7 @@ int batch_set_option(Batch* b, int option, int64_t value) {
             const int prev = b->mel_path;
             b->mel_path = (int)value;
             b->apply_mel_path();
-            if (b->k5_ok && stft5_lds_bytes(b->launch) > 163840) {
+            if (kernel_runs(*b, 5) && stft5_lds_bytes(b->launch) > kLdsMax) {
                 b->mel_path = prev;
                 b->apply_mel_path();
                 return set_error(THESIA_ERR_UNSUPPORTED, "the mel tables of that path do not fit LDS");
@@ -1048,51 +1086,42 @@ int batch_set_option(Batch* b, int option, int64_t value) {
 
 int batch_run(Batch* b, hipStream_t s) {
     if (!s) s = default_stream();
-    // per-track output ranges: folded into stft3's staged-row epilogue (linear kinds) and into
-    // kernel 7's (amp dB), else one reduction pass over the rows after the spectrogram launch
+    // the kernels enqueued on s read the track tables: their last use is marked on every return
+    // after the first enqueue, the error returns included (a later launch of this run may fail
+    // while an earlier kernel still reads the block on a caller's stream)
+    struct LastUse {
+        Batch* b;
+        hipStream_t s;
+        bool enqueued;
+        ~LastUse() { if (enqueued) b->d_tabs.used_on(s); }
+    } last_use{b, s, false};
     const uint64_t n_tr = b->frame0.empty() ? 0 : b->frame0.size() - 1;
-    const bool lin = b->launch.out_kind != OUT_COMPLEX && b->launch.out_kind != OUT_MEL &&
-                     b->launch.out_kind != OUT_MEL_AMP_DB;
-    bool in_kernel = false;
     if (b->range && launch_range_init(b->range, n_tr, s))
         return set_error(THESIA_ERR_DEVICE, "range init launch failed");
+    // the batch's kernel, then its fallbacks while a launch answers -2 (5 -> 3 -> 2 -> 1). Per-track
+    // output ranges: folded into the epilogue of the kernels that do that for these rows, else one
+    // reduction pass over the rows after the spectrogram launch
+    const KernelRow* k = kernel_row(b->kernel);
+    const char* name = k ? k->name : "stft";
     int rc = -2;
-    if (b->kernel == 9) {
-        rc = launch_stftx(b->launch, s);
-        if (rc) return set_error(rc == -2 ? THESIA_ERR_UNSUPPORTED : THESIA_ERR_DEVICE, "stftx launch failed");
-    } else if (b->kernel == 7) {
-        const bool r = b->plan->n_fft == 2048;
-        // amp dB rows fold their range into the epilogue (stftq / stftr RG instances)
-        const bool fold = b->range && b->launch.out_kind == OUT_AMP_DB;
+    bool folded = false;
+    for (; k && rc == -2; k = kernel_row(k->fallback)) {
+        const bool fold = b->range && k->folds_range(b->launch);
         b->launch.trk_range = fold ? b->range : nullptr;
-        rc = r ? launch_stftr(b->launch, s) : launch_stftq(b->launch, s);
-        in_kernel = fold && rc == 0;
+        rc = k->launch(b->launch, s);
         b->launch.trk_range = nullptr;
-        if (rc)
-            return set_error(rc == -2 ? THESIA_ERR_UNSUPPORTED : THESIA_ERR_DEVICE,
-                             r ? "stftr launch failed" : "stftq launch failed");
-    } else {
-        if (b->kernel == 5) rc = launch_stft5(b->launch, s);
-        if (rc == -2 && b->kernel >= 3) {
-            const bool fold = b->range && lin && b->launch.row_alt == 0;
-            b->launch.trk_range = fold ? b->range : nullptr;
-            rc = launch_stft3(b->launch, s);
-            in_kernel = fold && rc == 0;
-            b->launch.trk_range = nullptr;
-        }
-        if (rc == -2 && b->kernel >= 2) rc = launch_stft2(b->launch, s);
-        if (rc == -2) rc = launch_stft(b->launch, s);
-        if (rc == -2) return set_error(THESIA_ERR_UNSUPPORTED, "unsupported n_fft");
-        if (rc) return set_error(THESIA_ERR_DEVICE, std::string("stft launch failed: ") +
-                                                        hipGetErrorString(hipGetLastError()));
+        folded = fold && rc == 0;
     }
-    if (b->range && !in_kernel &&
+    if (rc == -2) return set_error(THESIA_ERR_UNSUPPORTED, std::string(name) + ": unsupported geometry");
+    if (rc) return set_error(THESIA_ERR_DEVICE, std::string(name) + " launch failed: " +
+                                                    hipGetErrorString(hipGetLastError()));
+#ifndef THESIA_DIAG_NO_LAST_USE  // (diagnostic build: the round-5 cache, for the test's control)
+    last_use.enqueued = true;
+#endif
+    if (b->range && !folded &&
         launch_range_rows(static_cast<const float*>(b->desc.d_output), b->launch.trk_frame0, n_tr,
                           (uint32_t)b->plan->row_bins(), b->range, s))
         return set_error(THESIA_ERR_DEVICE, "range launch failed");
-#ifndef THESIA_DIAG_NO_LAST_USE  // (diagnostic build: the round-5 cache, for the test's control)
-    b->d_tabs.used_on(s);  // the kernels just enqueued on s read the track tables
-#endif
     return THESIA_OK;
 }
 
@@ -1610,7 +1639,7 @@ void plan_stripe_ring(const std::vector<StripeTrack>& trk, uint32_t bins, uint32
     auto lds = [&]() { return render_stripe_lds_bytes(fc, tile, hdr, wts, waves, slots); };
     if (fc * nbmax > 64 * npf || lds() > (waves == 8 ? 81920 : 54613)) fc = 8;
     if (waves == 8 && lds() > 81920) waves = 4;
-    if (fc * nbmax > 64 * npf || lds() > 163840) return;
+    if (fc * nbmax > 64 * npf || lds() > kLdsMax) return;
     if (fc * (int)bins >= 65536 || tile * (fc + 4) >= 65536) return;
     g.stripe = true;
     g.st_kv = kv;
@@ -1695,7 +1724,7 @@ void plan_stripe(const std::vector<StripeTrack>& trk, uint32_t bins, uint32_t nh
     auto lds = [&]() { return render_stripe_lds_bytes(fc, tile, hdr, wts, waves); };
     if (fc * nbmax > 64 * npf || lds() > (waves == 8 ? 81920 : 54613)) fc = 8;
     if (waves == 8 && lds() > 81920) waves = 4;
-    if (fc * nbmax > 64 * npf || lds() > 163840) return;
+    if (fc * nbmax > 64 * npf || lds() > kLdsMax) return;
     // the kept element places (render_stripe.hip pk): a chunk's row offsets and the tile's float
     // indices below 2^16
     if (fc * (int)bins >= 65536 || tile * (fc + 4) >= 65536) return;

@@ -137,29 +137,12 @@ struct Batch {
     DevBuf d_tabs;  // [in_off | len | frame0] on the device (launch.trk_* point into it)
     uint64_t total_frames = 0;
     StftLaunch launch{};
-    // 1 stft_kernel, 2 stft2_kernel, 3 stft3_kernel, 5 stft5_kernel (streaming), 7 stftr_kernel
-    // (streaming, reference operation order), 9 stftx_kernel (reference operation order)
+    // 1 stft_kernel, 2 stft2_kernel, 3 stft3_kernel, 5 stft5_kernel (streaming), 7 stftr_kernel /
+    // stftq_kernel (streaming, reference operation order), 9 stftx_kernel (reference operation order)
     int kernel = 1;
-    bool k3_ok = false;  // the streaming kernel supports this batch's geometry
-    bool k5_ok = false;  // ... and so does its n_fft 2048 variant (stft5_kernel)
-    bool kr_ok = false;  // the reference-order streaming kernel (stftr_kernel) runs this batch
-    // automatic choice: stft5 for the mel kinds at n_fft 2048 and for linear rows without the
-    // range option (measured faster there: stereo power dB 5.64 vs 6.22 ms in round 3; slower for
-    // complex rows, 9.0 vs 6.98 ms, and stft3 folds the per-track range into its row epilogue;
-    // DESIGN.md §6), stft3 for the other streaming geometries, then the 4-waves/SIMD kernel for
-    // its sizes, else the general one
-    // at the viewer geometry (k5_view) stft5 pays only on large batches: its per-block setup
-    // (the packed mel stream, the rotation tables) against stft3's, measured at 48 kHz mel-128
-    // (profiles/r04_viewer/batch_size_ab.txt): 3.0e6 frames 4.48 vs 4.76 ms, 3.0e5 0.576 vs
-    // 0.570, 2.6e4 0.102 vs 0.077
-    static constexpr uint64_t kView5MinFrames = 400000;
-    bool k5_view = false;
-    int auto_kernel() const {
-        const bool mel = launch.out_kind == OUT_MEL || launch.out_kind == OUT_MEL_AMP_DB;
-        const bool lin = !mel && launch.out_kind != OUT_COMPLEX && !range;
-        const bool k5 = k5_ok && (mel || lin) && (!k5_view || total_frames >= kView5MinFrames);
-        return k5 ? 5 : k3_ok ? 3 : plan->use_v2 ? 2 : 1;
-    }
+    // the kernels that run this batch (engine.cpp's selection table, evaluated by batch_create):
+    // bit id of each THESIA_BATCH_OPT_KERNEL value; read through kernel_runs
+    uint32_t runs_mask = 0;
     bool kernel_forced = false;  // THESIA_BATCH_OPT_KERNEL set a kernel (else auto_kernel follows)
     // mel projection of stft5 (THESIA_BATCH_OPT_MEL_PATH): 0 automatic, 1 the rounds' chunk
     // stream (mel4p), 2 / 3 the packed stream with 2 / 3 float4 steps per chunk
@@ -175,6 +158,8 @@ int batches_run(Batch* const* b, size_t n, hipStream_t s);  // thesia_batches_ru
 int batches_policy();  // thesia_set_batches_policy
 int set_batches_policy(int policy);
 int batch_set_option(Batch* b, int option, int64_t value);  // thesia_batch_set_option
+bool kernel_runs(const Batch& b, int id);  // THESIA_BATCH_OPT_KERNEL would accept id for this batch
+int auto_kernel(const Batch& b);           // the kernel a batch runs when none is forced
 int ranges_read(const int* d_range, size_t n, float* mx, float* mn, int* nan, hipStream_t s);
 
 // display path selection (thesia_set_render_path): 0 fused batched launches (the single-pass

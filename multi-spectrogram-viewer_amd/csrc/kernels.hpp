@@ -111,6 +111,22 @@ struct StftLaunch {
     int* trk_range = nullptr;
 };
 
+// LDS a block can ask for on gfx950 (160 KiB per CU): the bound of every dynamic-LDS launch
+constexpr int kLdsMax = 163840;
+
+constexpr bool is_mel_kind(int out_kind) { return out_kind == OUT_MEL || out_kind == OUT_MEL_AMP_DB; }
+// the canonical geometry of the batch configs (the streaming kernels' ring hop; any other
+// geometry runs their viewer / DIR instances)
+inline bool canon_geometry(const StftLaunch& a) { return a.win == a.n_fft && a.hop * 4 == a.n_fft; }
+// what the reference-order streaming kernels (stftr / stftq) take at their n_fft: mono / stereo at
+// the canonical geometry (f32 / s16), or (DIR) f32 at any even win <= n_fft -- the frame start
+// t hop - n_fft / 2 is the reference's t hop - win / 2 - pad_left, lib.rs:400-401 -- and hop >= 1
+inline bool ref_stream_geometry(const StftLaunch& a) {
+    if (!(a.channels == 1 || a.channels == 2)) return false;
+    if (canon_geometry(a)) return a.in_format == IN_F32 || a.in_format == IN_S16;
+    return a.in_format == IN_F32 && a.hop >= 1 && a.win >= 2 && a.win <= a.n_fft && a.win % 2 == 0;
+}
+
 // stft5 stream region (floats) and where the packed mel stream stages a frame's mels in it:
 // behind the |X| row of F4 = 1028 floats; dummy slots follow the n_mels slots
 constexpr int kStft5Region = 1184, kMelpOut = 1028, kMelpDummies = 16;
@@ -136,15 +152,17 @@ int launch_stft(const StftLaunch& a, hipStream_t stream);
 int launch_stft2(const StftLaunch& a, hipStream_t stream);
 bool stft2_supports(int n_fft);
 int stft2_kernel_info(int n_fft, int* lds_bytes, int* tile_frames, int* lanes_per_frame);
-// stft3_kernel (streaming; win = n_fft, hop = n_fft/4, f32 mono/stereo): 0 on success, -2 when
-// the geometry is not its own (or the mel rows do not fit LDS).
+// The streaming kernels: X_supports(a), the launch's geometry / format / channels is one of the
+// kernel's instances; X_lds_bytes(a), its dynamic LDS (> kLdsMax: cannot run); launch_X: 0, -2
+// when the kernel does not run the launch, -1 on a device error.
+// stft3_kernel (win = n_fft, hop = n_fft/4, or a viewer geometry: stft3v below)
 int launch_stft3(const StftLaunch& a, hipStream_t stream);
-bool stft3_supports(int n_fft, int win, int hop, int in_format, int channels);
-int stft3_lds_bytes(const StftLaunch& a);  // dynamic LDS of the launch (> 163840: cannot run)
+bool stft3_supports(const StftLaunch& a);
+int stft3_lds_bytes(const StftLaunch& a);
 // the streaming kernel at the viewer geometries (stft3v_kernels.hip: win = 4 hop < n_fft, even
 // hop; launch_stft3 / stft3_supports / stft3_lds_bytes dispatch to these)
 int launch_stft3v(const StftLaunch& a, hipStream_t stream);
-bool stft3v_supports(int n_fft, int win, int hop, int in_format, int channels);
+bool stft3v_supports(const StftLaunch& a);
 int stft3v_lds_bytes(const StftLaunch& a);
 // stftx_kernel (every n_fft: the reference's operation order, bit-exact with the oracle)
 int launch_stftx(const StftLaunch& a, hipStream_t stream);
@@ -154,21 +172,29 @@ int stftx_lds_bytes(int n_fft, bool mel);
 // length's Plan (xpos, forward twiddles, sin_cos, base butterfly_8 twiddles)
 int launch_irfftx(const float* in, uint64_t n_frames, int length, const int* xpos, const float* tw1,
                   const float* sincos, const float* xw8, float* out, hipStream_t s);
-// stft5_kernel (streaming, n_fft 2048 only, co-resident untangle pairs; stft5_kernels.hip)
+// stft5_kernel (n_fft 2048 only, co-resident untangle pairs; stft5_kernels.hip)
 int launch_stft5(const StftLaunch& a, hipStream_t stream);
-bool stft5_supports(int n_fft, int win, int hop, int in_format, int channels);
+bool stft5_supports(const StftLaunch& a);
 int stft5_lds_bytes(const StftLaunch& a);
-// stftr_kernel (streaming, reference operation order: rows equal the oracle's bit for bit;
-// n_fft 2048, win = n_fft, hop = n_fft / 4; stftr_kernels.hip)
+// stftr_kernel (n_fft 2048, reference operation order: rows equal the oracle's bit for bit;
+// stftr_kernels.hip) at ref_stream_geometry's two families: the canonical geometry streams its
+// input through a register ring; the others (DIR: the viewer's own geometries, f32 only) load
+// every frame's samples, the centring pads of win < n_fft masked to +0. Mel kinds need the
+// 64-lane packed stream (melr_chunks > 0).
 int launch_stftr(const StftLaunch& a, hipStream_t stream);
-bool stftr_supports(int n_fft, int win, int hop, int in_format, int channels);
+bool stftr_supports(const StftLaunch& a);
 int stftr_lds_bytes(const StftLaunch& a);
 constexpr int stftr_region_floats() { return 16 * 130; }  // GeoR::REGION
-// stftq_kernel (the same contract for n_fft 256 / 512 / 1024, win = n_fft, hop = n_fft / 4;
-// stftq_kernels.hip): batch kernel 7 at those sizes
+// stftq_kernel (the same contract and families for n_fft 256 / 512 / 1024; stftq_kernels.hip).
+// Mel kinds need the reference-order band tables (xmel_*).
 int launch_stftq(const StftLaunch& a, hipStream_t stream);
-bool stftq_supports(int n_fft, int win, int hop, int in_format, int channels);
+bool stftq_supports(const StftLaunch& a);
 int stftq_lds_bytes(const StftLaunch& a);
+// batch kernel 7, the reference-order streaming kernel of the launch's n_fft: stftr at 2048,
+// stftq at 256 / 512 / 1024 (stftr_kernels.hip holds the split)
+int launch_stft7(const StftLaunch& a, hipStream_t stream);
+bool stft7_supports(const StftLaunch& a);
+int stft7_lds_bytes(const StftLaunch& a);
 // LDS bytes / frames per block pass / lanes per frame of the kernel for n_fft.
 int stft_kernel_info(int n_fft, int* lds_bytes, int* tile_frames, int* lanes_per_frame);
 

@@ -206,7 +206,7 @@ int MultiTrack::add_tracks(const std::vector<uint64_t>& ids, const std::vector<P
         // geometries; stft5 for the 48 kHz rows of batches of >= 400 000 frames), held to the e2e
         // contract relative to the reference's own f32 error (tests/test_gpu_parity.py
         // _check_multitrack)
-        rc = batch_set_option(b, THESIA_BATCH_OPT_KERNEL, fast_ ? 0 : b->kr_ok ? 7 : 9);
+        rc = batch_set_option(b, THESIA_BATCH_OPT_KERNEL, fast_ ? 0 : kernel_runs(*b, 7) ? 7 : 9);
         if (!rc) rc = batch_set_option(b, THESIA_BATCH_OPT_RANGE, (int64_t)(uintptr_t)(rng.as<int>() + 3 * t_rng));
         t_rng += idx.size();
         if (!rc) rc = batch_run(b, s);

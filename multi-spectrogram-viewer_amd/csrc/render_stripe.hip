@@ -530,7 +530,7 @@ int launch_render_stripe(const StripeLaunch& L, hipStream_t s) {
     if (!kern) return -2;
     const int lds = render_stripe_lds_bytes(L.fc, L.tile_cap, L.hdr_cap, L.wts_cap, L.waves,
                                             L.hg ? L.ring + 4 * L.hg + 1 : 0);
-    if (lds > 163840) return -2;
+    if (lds > kLdsMax) return -2;
     if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -1;
     const uint32_t rows = 64u * (uint32_t)L.waves;
     const dim3 grid((L.nw_max + L.strip - 1) / L.strip, (L.nh + rows - 1) / rows, L.n);

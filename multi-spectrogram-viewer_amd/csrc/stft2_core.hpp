@@ -31,7 +31,7 @@ struct Geo2 {
     static_assert(P % L == 0 && L >= 8, "stft2 geometry");
     static_assert(XREG >= F4 && XREG >= NC, "the |X| row and the load staging must fit a region");
     static_assert(RS % 4 == 0, "16-byte aligned regions");
-    static_assert(2 * LDS_BYTES <= 163840, "two blocks per CU");
+    static_assert(2 * LDS_BYTES <= kLdsMax, "two blocks per CU");
 };
 
 // One point's worth of input per lane (2 samples x C interleaved channels) and its downmix:

@@ -164,7 +164,7 @@ static int launch2_k(const StftLaunch& a, hipStream_t stream) {
 template <int NC, int INF>
 static int launch2_fmt(const StftLaunch& a, hipStream_t s) {
     if (a.out_kind == OUT_COMPLEX) return launch2_k<NC, 0, INF>(a, s);
-    if (a.out_kind == OUT_MEL || a.out_kind == OUT_MEL_AMP_DB) return launch2_k<NC, 2, INF>(a, s);
+    if (is_mel_kind(a.out_kind)) return launch2_k<NC, 2, INF>(a, s);
     return launch2_k<NC, 1, INF>(a, s);
 }
 

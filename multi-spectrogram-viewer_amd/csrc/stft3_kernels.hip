@@ -80,22 +80,8 @@ static int launch3_k(const StftLaunch& a, hipStream_t stream) {
     if constexpr (VAR == 0 && WV == kWaves && NC == 1024 && OK == 1 && C == 2 && INF == IN_F32) {
         if (a.row_alt == 1) return launch3_k<NC, OK, C, INF, 1024>(a, stream);
     }
-    constexpr int kBlock = 64 * WV;
-    const int lds = lds3_bytes<NC, OK, VAR, WV>(a);
-    if (lds > 163840) return -2;
-    auto kern = stft3_kernel<NC, OK, C, INF, VAR, WV>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return -1;
-    if (a.total_frames == 0) return 0;
-    constexpr uint64_t per_block = Geo3<NC, WV>::STREAMS;
-    int grid = grid_for(reinterpret_cast<const void*>(kern), kBlock, lds,
-                        (a.total_frames + per_block - 1) / per_block, a.grid, a.grid_share);
-    const uint64_t streams = (uint64_t)grid * per_block;
-    const uint64_t fps = (a.total_frames + streams - 1) / streams;
-    grid = (int)((a.total_frames + fps * per_block - 1) / (fps * per_block));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, stream, a, fps);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_streams(stft3_kernel<NC, OK, C, INF, VAR, WV>, 64 * WV, lds3_bytes<NC, OK, VAR, WV>(a),
+                          Geo3<NC, WV>::STREAMS, a, stream);
 }
 
 #ifndef THESIA_WV3_SMALL
@@ -106,7 +92,7 @@ static int launch3_c(const StftLaunch& a, hipStream_t s) {
     // linear kinds of mono input at n_fft <= 512 fit 168 VGPRs without spills
     constexpr int WVS = NC <= 256 && C == 1 ? THESIA_WV3_SMALL : kWaves;
     if (a.out_kind == OUT_COMPLEX) return launch3_k<NC, 0, C, INF>(a, s);
-    if (a.out_kind == OUT_MEL || a.out_kind == OUT_MEL_AMP_DB) return launch3_k<NC, 2, C, INF>(a, s);
+    if (is_mel_kind(a.out_kind)) return launch3_k<NC, 2, C, INF>(a, s);
     // amp dB (the default kind, the C5 / viewer rows): the kind and the range fold at compile
     // time (stft3_kernel.hpp, VAR bits 18-21)
     bool fixed = a.out_kind == OUT_AMP_DB && a.row_alt == 0;
@@ -121,17 +107,9 @@ static int launch3_c(const StftLaunch& a, hipStream_t s) {
     return launch3_k<NC, 1, C, INF, 0, WVS>(a, s);
 }
 
-template <int NC>
-static int launch3_nc(const StftLaunch& a, hipStream_t s) {
-    if (a.in_format == IN_S16)
-        return a.channels == 2 ? launch3_c<NC, 2, IN_S16>(a, s) : launch3_c<NC, 1, IN_S16>(a, s);
-    return a.channels == 2 ? launch3_c<NC, 2, IN_F32>(a, s) : launch3_c<NC, 1, IN_F32>(a, s);
-}
-
 int stft3_lds_bytes(const StftLaunch& a) {
-    if (stft3v_supports(a.n_fft, a.win, a.hop, a.in_format, a.channels)) return stft3v_lds_bytes(a);
-    const bool mel = a.out_kind == OUT_MEL || a.out_kind == OUT_MEL_AMP_DB;
-    const int ok = a.out_kind == OUT_COMPLEX ? 0 : mel ? 2 : 1;
+    if (stft3v_supports(a)) return stft3v_lds_bytes(a);
+    const int ok = a.out_kind == OUT_COMPLEX ? 0 : is_mel_kind(a.out_kind) ? 2 : 1;
     switch (a.n_fft / 2) {
         case 128: return ok == 0 ? lds3_bytes<128, 0, 0>(a) : ok == 1 ? lds3_bytes<128, 1, 0>(a) : lds3_bytes<128, 2, 0>(a);
         case 256: return ok == 0 ? lds3_bytes<256, 0, 0>(a) : ok == 1 ? lds3_bytes<256, 1, 0>(a) : lds3_bytes<256, 2, 0>(a);
@@ -141,23 +119,25 @@ int stft3_lds_bytes(const StftLaunch& a) {
     }
 }
 
-bool stft3_supports(int n_fft, int win, int hop, int in_format, int channels) {
-    return ((n_fft == 256 || n_fft == 512 || n_fft == 1024 || n_fft == 2048) && win == n_fft &&
-            hop * 4 == n_fft && (in_format == IN_F32 || in_format == IN_S16) &&
-            (channels == 1 || channels == 2)) ||
-           stft3v_supports(n_fft, win, hop, in_format, channels);  // the viewer geometries
+bool stft3_supports(const StftLaunch& a) {
+    return ((a.n_fft == 256 || a.n_fft == 512 || a.n_fft == 1024 || a.n_fft == 2048) && canon_geometry(a) &&
+            (a.in_format == IN_F32 || a.in_format == IN_S16) && (a.channels == 1 || a.channels == 2)) ||
+           stft3v_supports(a);  // the viewer geometries
 }
 
 int launch_stft3(const StftLaunch& a, hipStream_t s) {
-    if (stft3v_supports(a.n_fft, a.win, a.hop, a.in_format, a.channels)) return launch_stft3v(a, s);
-    if (a.win != a.n_fft || a.hop * 4 != a.n_fft) return -2;
-    switch (a.n_fft / 2) {
-        case 128: return launch3_nc<128>(a, s);
-        case 256: return launch3_nc<256>(a, s);
-        case 512: return launch3_nc<512>(a, s);
-        case 1024: return launch3_nc<1024>(a, s);
-        default: return -2;
-    }
+    if (stft3v_supports(a)) return launch_stft3v(a, s);
+    if (!canon_geometry(a)) return -2;
+    return for_channels_format(a, [&](auto c, auto inf) {
+        constexpr int C = decltype(c)::value, INF = decltype(inf)::value;
+        switch (a.n_fft / 2) {
+            case 128: return launch3_c<128, C, INF>(a, s);
+            case 256: return launch3_c<256, C, INF>(a, s);
+            case 512: return launch3_c<512, C, INF>(a, s);
+            case 1024: return launch3_c<1024, C, INF>(a, s);
+            default: return -2;
+        }
+    });
 }
 
 }  // namespace thesia

@@ -26,22 +26,8 @@ int lds3v_bytes(const StftLaunch& a) {
 
 template <int NC, int HQ, int OK, int C, int INF, int VAR, int WV, int VODD>
 int launch3v_k(const StftLaunch& a, hipStream_t stream) {
-    constexpr int kBlock = 64 * WV;
-    const int lds = lds3v_bytes<NC, OK, VAR, WV>(a);
-    if (lds > 163840) return -2;
-    auto kern = stft3_kernel<NC, OK, C, INF, VAR, WV, HQ, VODD>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return -1;
-    if (a.total_frames == 0) return 0;
-    constexpr uint64_t per_block = Geo3<NC, WV>::STREAMS;
-    int grid = grid_for(reinterpret_cast<const void*>(kern), kBlock, lds,
-                        (a.total_frames + per_block - 1) / per_block, a.grid, a.grid_share);
-    const uint64_t streams = (uint64_t)grid * per_block;
-    const uint64_t fps = (a.total_frames + streams - 1) / streams;
-    grid = (int)((a.total_frames + fps * per_block - 1) / (fps * per_block));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, stream, a, fps);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_streams(stft3_kernel<NC, OK, C, INF, VAR, WV, HQ, VODD>, 64 * WV,
+                          lds3v_bytes<NC, OK, VAR, WV>(a), Geo3<NC, WV>::STREAMS, a, stream);
 }
 
 template <int NC, int HQ, int C, int INF, int VODD>
@@ -50,7 +36,7 @@ int launch3v_c(const StftLaunch& a, hipStream_t s) {
     // stream's rows are not contiguous), 12-wave blocks for mono linear kinds at n_fft <= 512
     constexpr int WVS = NC <= 256 && C == 1 ? 12 : kWaves;
     if (a.out_kind == OUT_COMPLEX) return launch3v_k<NC, HQ, 0, C, INF, VODD ? 1024 : 2048, kWaves, VODD>(a, s);
-    if (a.out_kind == OUT_MEL || a.out_kind == OUT_MEL_AMP_DB) return launch3v_k<NC, HQ, 2, C, INF, 0, kWaves, VODD>(a, s);
+    if (is_mel_kind(a.out_kind)) return launch3v_k<NC, HQ, 2, C, INF, 0, kWaves, VODD>(a, s);
     // amp dB rows without the range fold (the viewer's): the kind at compile time (VAR bits 18-20)
     bool fixed = a.out_kind == OUT_AMP_DB && !a.trk_range;
 #ifdef THESIA_EXPERIMENTS
@@ -58,20 +44,6 @@ int launch3v_c(const StftLaunch& a, hipStream_t s) {
 #endif
     if (fixed) return launch3v_k<NC, HQ, 1, C, INF, OUT_AMP_DB << 18, WVS, VODD>(a, s);
     return launch3v_k<NC, HQ, 1, C, INF, 0, WVS, VODD>(a, s);
-}
-
-template <int NC, int HQ>
-int launch3v_nc(const StftLaunch& a, hipStream_t s) {
-    if (a.in_format == IN_S16)
-        return a.channels == 2 ? launch3v_c<NC, HQ, 2, IN_S16, 0>(a, s) : launch3v_c<NC, HQ, 1, IN_S16, 0>(a, s);
-    return a.channels == 2 ? launch3v_c<NC, HQ, 2, IN_F32, 0>(a, s) : launch3v_c<NC, HQ, 1, IN_F32, 0>(a, s);
-}
-
-template <int NC, int HQ>
-int launch3v_nc_odd(const StftLaunch& a, hipStream_t s) {
-    if (a.in_format == IN_S16)
-        return a.channels == 2 ? launch3v_c<NC, HQ, 2, IN_S16, 1>(a, s) : launch3v_c<NC, HQ, 1, IN_S16, 1>(a, s);
-    return a.channels == 2 ? launch3v_c<NC, HQ, 2, IN_F32, 1>(a, s) : launch3v_c<NC, HQ, 1, IN_F32, 1>(a, s);
 }
 
 // the instantiated (NC, rows per stream hop) pairs; odd hops: a stream hop of 2 hop samples
@@ -90,17 +62,16 @@ int view_rows(int n_fft, int hop) {
 
 }  // namespace
 
-bool stft3v_supports(int n_fft, int win, int hop, int in_format, int channels) {
+bool stft3v_supports(const StftLaunch& a) {
     // the streaming start rule (frame start = t hop - n_fft / 2) needs win / 2 + pad_left =
     // n_fft / 2, i.e. an even win (lib.rs:400-401); the canonical geometry is stft3's own
-    return view_rows(n_fft, hop) > 0 && win <= n_fft && win % 2 == 0 && win >= 2 &&
-           !(win == n_fft && hop * 4 == n_fft) && (in_format == IN_F32 || in_format == IN_S16) &&
-           (channels == 1 || channels == 2);
+    return view_rows(a.n_fft, a.hop) > 0 && a.win <= a.n_fft && a.win % 2 == 0 && a.win >= 2 &&
+           !canon_geometry(a) && (a.in_format == IN_F32 || a.in_format == IN_S16) &&
+           (a.channels == 1 || a.channels == 2);
 }
 
 int stft3v_lds_bytes(const StftLaunch& a) {
-    const bool mel = a.out_kind == OUT_MEL || a.out_kind == OUT_MEL_AMP_DB;
-    const int ok = a.out_kind == OUT_COMPLEX ? 0 : mel ? 2 : 1;
+    const int ok = a.out_kind == OUT_COMPLEX ? 0 : is_mel_kind(a.out_kind) ? 2 : 1;
     switch (a.n_fft / 2) {
         case 256: return ok == 0 ? lds3v_bytes<256, 0, 2048, kWaves>(a) : ok == 1 ? lds3v_bytes<256, 1, 0, kWaves>(a) : lds3v_bytes<256, 2, 0, kWaves>(a);
         case 512: return ok == 0 ? lds3v_bytes<512, 0, 2048, kWaves>(a) : ok == 1 ? lds3v_bytes<512, 1, 0, kWaves>(a) : lds3v_bytes<512, 2, 0, kWaves>(a);
@@ -110,15 +81,18 @@ int stft3v_lds_bytes(const StftLaunch& a) {
 }
 
 int launch_stft3v(const StftLaunch& a, hipStream_t s) {
-    switch (a.n_fft / 2 * 16 + view_rows(a.n_fft, a.hop)) {
-        case 1024 * 16 + 7: return launch3v_nc<1024, 7>(a, s);
-        case 512 * 16 + 7: return launch3v_nc<512, 7>(a, s);
-        case 512 * 16 + 5: return launch3v_nc<512, 5>(a, s);
-        case 256 * 16 + 2: return launch3v_nc<256, 2>(a, s);
-        case 1024 * 16 + 13: return launch3v_nc_odd<1024, 13>(a, s);
-        case 512 * 16 + 13: return launch3v_nc_odd<512, 13>(a, s);
-        default: return -2;
-    }
+    return for_channels_format(a, [&](auto c, auto inf) {
+        constexpr int C = decltype(c)::value, INF = decltype(inf)::value;
+        switch (a.n_fft / 2 * 16 + view_rows(a.n_fft, a.hop)) {
+            case 1024 * 16 + 7: return launch3v_c<1024, 7, C, INF, 0>(a, s);
+            case 512 * 16 + 7: return launch3v_c<512, 7, C, INF, 0>(a, s);
+            case 512 * 16 + 5: return launch3v_c<512, 5, C, INF, 0>(a, s);
+            case 256 * 16 + 2: return launch3v_c<256, 2, C, INF, 0>(a, s);
+            case 1024 * 16 + 13: return launch3v_c<1024, 13, C, INF, 1>(a, s);  // odd hops
+            case 512 * 16 + 13: return launch3v_c<512, 13, C, INF, 1>(a, s);
+            default: return -2;
+        }
+    });
 }
 
 }  // namespace thesia

@@ -674,7 +674,7 @@ template <int OK, int VAR = 0>
 static int region_stride5(const StftLaunch& a) {
     // the packed mel stream stages the frame's mels behind the |X| row: full regions only
     if (OK == 2 && a.melp_chunks > 0) return Geo5::RS;
-    return lds5_bytes<OK, VAR>(a, Geo5::RS) <= 163840 ? Geo5::RS : Geo5::RS_MIN;
+    return lds5_bytes<OK, VAR>(a, Geo5::RS) <= kLdsMax ? Geo5::RS : Geo5::RS_MIN;
 }
 
 template <int OK, int C, int INF, int VAR = 0, int HQ = 0>
@@ -686,35 +686,21 @@ static int launch5_k(const StftLaunch& a, hipStream_t stream) {
     }
 #endif
     const int rs = region_stride5<OK, VAR>(a);
-    const int lds = lds5_bytes<OK, VAR>(a, rs);
-    if (lds > 163840) return -2;
-    auto kern = stft5_kernel<OK, C, INF, VAR, HQ>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return -1;
-    if (a.total_frames == 0) return 0;
-    constexpr uint64_t per_block = Geo5::STREAMS;
-    int grid = grid_for(reinterpret_cast<const void*>(kern), Geo5::BLOCK, lds,
-                        (a.total_frames + per_block - 1) / per_block, a.grid, a.grid_share);
-    const uint64_t streams = (uint64_t)grid * per_block;
-    const uint64_t fps = (a.total_frames + streams - 1) / streams;
-    grid = (int)((a.total_frames + fps * per_block - 1) / (fps * per_block));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(Geo5::BLOCK), lds, stream, a, fps, rs);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_streams(stft5_kernel<OK, C, INF, VAR, HQ>, Geo5::BLOCK, lds5_bytes<OK, VAR>(a, rs),
+                          Geo5::STREAMS, a, stream, rs);
 }
 
-// the viewer geometry (HQ 7: hop 480, win <= 2048) for the mel and linear kinds (complex rows
-// stay on stft3, which is faster for them)
-static bool view5(const StftLaunch& a) { return !(a.win == 2048 && a.hop * 4 == 2048); }
 template <int C, int INF>
 static int launch5_c(const StftLaunch& a, hipStream_t s) {
-    const bool mel = a.out_kind == OUT_MEL || a.out_kind == OUT_MEL_AMP_DB;
+    const bool mel = is_mel_kind(a.out_kind);
     bool fixed = a.out_kind == OUT_AMP_DB;  // amp dB rows: the kind at compile time
 #ifdef THESIA_EXPERIMENTS
     if (getenv("THESIA_STFT3_RTKIND")) fixed = false;  // A/B: the run-time kind
 #endif
     constexpr int KDB = OUT_AMP_DB << 18;
-    if (view5(a)) {
+    // the viewer geometry (HQ 7: hop 480, win <= 2048) for the mel and linear kinds (complex rows
+    // stay on stft3, which is faster for them)
+    if (!canon_geometry(a)) {
         if (a.out_kind == OUT_COMPLEX) return -2;
         if (mel) return launch5_k<2, C, INF, 0, 7>(a, s);
         return fixed ? launch5_k<1, C, INF, KDB, 7>(a, s) : launch5_k<1, C, INF, 0, 7>(a, s);
@@ -725,25 +711,24 @@ static int launch5_c(const StftLaunch& a, hipStream_t s) {
 }
 
 int stft5_lds_bytes(const StftLaunch& a) {
-    const bool mel = a.out_kind == OUT_MEL || a.out_kind == OUT_MEL_AMP_DB;
     return a.out_kind == OUT_COMPLEX ? lds5_bytes<0>(a, region_stride5<0>(a))
-           : mel ? lds5_bytes<2>(a, region_stride5<2>(a)) : lds5_bytes<1>(a, region_stride5<1>(a));
+           : is_mel_kind(a.out_kind) ? lds5_bytes<2>(a, region_stride5<2>(a)) : lds5_bytes<1>(a, region_stride5<1>(a));
 }
 
-bool stft5_supports(int n_fft, int win, int hop, int in_format, int channels) {
+bool stft5_supports(const StftLaunch& a) {
     // the canonical geometry, or the 48 kHz viewer one (hop / 2 = 7 rows of 32 + 16; an even win
-    // <= n_fft, as the streaming start rule needs, stft3v_kernels.hip)
-    const bool canon = win == n_fft && hop * 4 == n_fft;
-    const bool view = hop % 2 == 0 && (hop / 2) / 32 == 7 && win <= n_fft && win % 2 == 0 && win >= 2;
-    return n_fft == 2048 && (canon || view) && (in_format == IN_F32 || in_format == IN_S16) &&
-           (channels == 1 || channels == 2);
+    // <= n_fft, as the streaming start rule needs, stft3v_kernels.hip) for real rows
+    const bool view = a.hop % 2 == 0 && (a.hop / 2) / 32 == 7 && a.win <= a.n_fft && a.win % 2 == 0 &&
+                      a.win >= 2 && a.out_kind != OUT_COMPLEX;
+    return a.n_fft == 2048 && (canon_geometry(a) || view) && (a.in_format == IN_F32 || a.in_format == IN_S16) &&
+           (a.channels == 1 || a.channels == 2);
 }
 
 int launch_stft5(const StftLaunch& a, hipStream_t s) {
     if (a.n_fft != 2048) return -2;
-    if (a.in_format == IN_S16)
-        return a.channels == 2 ? launch5_c<2, IN_S16>(a, s) : launch5_c<1, IN_S16>(a, s);
-    return a.channels == 2 ? launch5_c<2, IN_F32>(a, s) : launch5_c<1, IN_F32>(a, s);
+    return for_channels_format(a, [&](auto c, auto inf) {
+        return launch5_c<decltype(c)::value, decltype(inf)::value>(a, s);
+    });
 }
 
 }  // namespace thesia

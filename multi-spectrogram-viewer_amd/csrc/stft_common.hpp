@@ -216,4 +216,41 @@ inline int grid_for(const void* kern, int block, int lds, uint64_t n_tiles, int 
     return grid;
 }
 
+// The launch tail of the streaming kernels (stft3 / stft3v / stft5 / stftr / stftq): blocks of
+// `block` threads with `lds` bytes of dynamic LDS, per_block frame streams each; kern(a, fps,
+// extra...) walks fps consecutive frames per stream. One occupancy wave of blocks (grid_for),
+// then the fewest blocks that cover the batch at that wave's frames per stream. -2: the LDS
+// does not fit (the caller falls back to another kernel), -1: device error, 0: enqueued.
+template <class K, class... Extra>
+inline int launch_streams(K kern, int block, int lds, uint64_t per_block, const StftLaunch& a,
+                          hipStream_t stream, Extra... extra) {
+    if (lds > kLdsMax) return -2;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+        return -1;
+    if (a.total_frames == 0) return 0;
+    int grid = grid_for(reinterpret_cast<const void*>(kern), block, lds,
+                        (a.total_frames + per_block - 1) / per_block, a.grid, a.grid_share);
+    const uint64_t streams = (uint64_t)grid * per_block;
+    const uint64_t fps = (a.total_frames + streams - 1) / streams;
+    grid = (int)((a.total_frames + fps * per_block - 1) / (fps * per_block));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, a, fps, extra...);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// f(integral_constant C, integral_constant INF) for the launch's channels (2: stereo, else mono)
+// and input format, in the style of static_for: the caller's generic lambda names the template
+// instance. F32_ONLY: the f32 instances whatever the format (the DIR paths have no others).
+template <bool F32_ONLY = false, class F>
+inline int for_channels_format(const StftLaunch& a, F&& f) {
+    constexpr std::integral_constant<int, 1> c1{};
+    constexpr std::integral_constant<int, 2> c2{};
+    if constexpr (!F32_ONLY) {
+        constexpr std::integral_constant<int, IN_S16> s16{};
+        if (a.in_format == IN_S16) return a.channels == 2 ? f(c2, s16) : f(c1, s16);
+    }
+    constexpr std::integral_constant<int, IN_F32> f32{};
+    return a.channels == 2 ? f(c2, f32) : f(c1, f32);
+}
+
 }  // namespace thesia

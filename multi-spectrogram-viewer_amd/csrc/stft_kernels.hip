@@ -309,7 +309,7 @@ stft_kernel(StftLaunch a, uint64_t tiles_per_block) {
 // --------------------------------------------------------------------------------------
 static int ok_of(int out_kind) {
     if (out_kind == OUT_COMPLEX) return 0;
-    if (out_kind == OUT_MEL || out_kind == OUT_MEL_AMP_DB) return 2;
+    if (is_mel_kind(out_kind)) return 2;
     return 1;
 }
 

@@ -737,26 +737,13 @@ static int launchq_k(const StftLaunch& a, hipStream_t s) {
         if (v == 16) return launchq_k<NC, KIND, C, INF, WV, 16, DIR, RG>(a, s);
     }
 #endif
-    const int lds = ldsq_bytes<NC>(WV, DIR);
-    if (lds > 163840) return -2;
-    auto kern = stftq_kernel<NC, KIND, C, INF, WV, VAR, DIR, RG>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-        hipSuccess)
-        return -1;
-    if (a.total_frames == 0) return 0;
-    constexpr uint64_t per_block = (uint64_t)WV * GeoQ<NC>::FPW;
-    int grid = grid_for(reinterpret_cast<const void*>(kern), 64 * WV, lds, (a.total_frames + per_block - 1) / per_block,
-                        a.grid, a.grid_share);
-    const uint64_t streams = (uint64_t)grid * per_block;
-    const uint64_t fps = (a.total_frames + streams - 1) / streams;
-    grid = (int)((a.total_frames + fps * per_block - 1) / (fps * per_block));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WV), lds, s, a, fps);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_streams(stftq_kernel<NC, KIND, C, INF, WV, VAR, DIR, RG>, 64 * WV, ldsq_bytes<NC>(WV, DIR),
+                          (uint64_t)WV * GeoQ<NC>::FPW, a, s);
 }
 
 template <int NC, int C, int INF, bool DIR = false>
 static int launchq_c(const StftLaunch& a, hipStream_t s) {
-    if ((a.out_kind == OUT_MEL || a.out_kind == OUT_MEL_AMP_DB) && (!a.xmel_band || !a.xmel_w)) return -2;
+    if (is_mel_kind(a.out_kind) && (!a.xmel_band || !a.xmel_w)) return -2;
     // 16-wave blocks (4 waves / SIMD, <= 128 VGPRs) for n_fft 512 / 1024: 3.59 -> 3.48 and 3.88
     // -> 3.70 ms on 1000 x 10 s amp-dB tracks; n_fft 256 stays at 12 (3.54 vs 3.69;
     // profiles/r05_stftq/ablations.txt)
@@ -776,34 +763,31 @@ static int launchq_c(const StftLaunch& a, hipStream_t s) {
 }
 
 // the canonical C5 geometry streams (win = n_fft, hop = n_fft / 4); any other (DIR) loads per frame
-static bool q_canon(const StftLaunch& a) { return a.win == a.n_fft && a.hop * 4 == a.n_fft; }
-
-template <int NC>
+template <int C, int INF, bool DIR = false>
 static int launchq_n(const StftLaunch& a, hipStream_t s) {
-    if (!q_canon(a))  // the viewer's geometries: f32 mono / stereo (MultiTrack's mono pool)
-        return a.channels == 2 ? launchq_c<NC, 2, IN_F32, true>(a, s) : launchq_c<NC, 1, IN_F32, true>(a, s);
-    if (a.in_format == IN_S16) return a.channels == 2 ? launchq_c<NC, 2, IN_S16>(a, s) : launchq_c<NC, 1, IN_S16>(a, s);
-    return a.channels == 2 ? launchq_c<NC, 2, IN_F32>(a, s) : launchq_c<NC, 1, IN_F32>(a, s);
+    if (a.n_fft == 256) return launchq_c<128, C, INF, DIR>(a, s);
+    if (a.n_fft == 512) return launchq_c<256, C, INF, DIR>(a, s);
+    return launchq_c<512, C, INF, DIR>(a, s);
 }
 
-bool stftq_supports(int n_fft, int win, int hop, int in_format, int channels) {
-    if (!(n_fft == 256 || n_fft == 512 || n_fft == 1024) || !(channels == 1 || channels == 2)) return false;
-    if (win == n_fft && hop * 4 == n_fft) return in_format == IN_F32 || in_format == IN_S16;
-    // any other geometry (DIR): even win <= n_fft (the frame start t hop - n_fft / 2 is the
-    // reference's t hop - win / 2 - pad_left, lib.rs:400-401), f32
-    return in_format == IN_F32 && hop >= 1 && win >= 2 && win <= n_fft && win % 2 == 0;
+bool stftq_supports(const StftLaunch& a) {
+    return (a.n_fft == 256 || a.n_fft == 512 || a.n_fft == 1024) && ref_stream_geometry(a);
 }
 
 int stftq_lds_bytes(const StftLaunch& a) {
-    const bool dir = !q_canon(a);
+    const bool dir = !canon_geometry(a);
     return a.n_fft == 256 ? ldsq_bytes<128>(12, dir) : a.n_fft == 512 ? ldsq_bytes<256>(16, dir) : ldsq_bytes<512>(16, dir);
 }
 
 int launch_stftq(const StftLaunch& a, hipStream_t s) {
-    if (!stftq_supports(a.n_fft, a.win, a.hop, a.in_format, a.channels)) return -2;
-    if (a.n_fft == 256) return launchq_n<128>(a, s);
-    if (a.n_fft == 512) return launchq_n<256>(a, s);
-    return launchq_n<512>(a, s);
+    if (!stftq_supports(a)) return -2;
+    if (!canon_geometry(a))  // the viewer's geometries: f32 mono / stereo (MultiTrack's mono pool)
+        return for_channels_format<true>(a, [&](auto c, auto inf) {
+            return launchq_n<decltype(c)::value, decltype(inf)::value, true>(a, s);
+        });
+    return for_channels_format(a, [&](auto c, auto inf) {
+        return launchq_n<decltype(c)::value, decltype(inf)::value>(a, s);
+    });
 }
 
 }  // namespace thesia

@@ -454,13 +454,12 @@ stftr_kernel(StftLaunch a, uint64_t fps) {
 // host side
 // ------------------------------------------------------------------------------------------
 // the canonical geometry streams (win = n_fft, hop = n_fft / 4); any other (DIR) loads per frame
-static bool r_canon(const StftLaunch& a) { return a.win == a.n_fft && a.hop * 4 == a.n_fft; }
-
 static int ldsr_bytes(const StftLaunch& a, int wv) {
-    const bool mel = a.out_kind == OUT_MEL || a.out_kind == OUT_MEL_AMP_DB;
-    const int meltab = mel ? ((a.melr_chunks + 2) + (a.melr_chunks + 1) * a.melr_steps) * GeoR::L * 16 : 0;
-    return (GeoR::TAB_FLOATS + (r_canon(a) ? 0 : GeoR::WL_FLOATS) + wv * GeoR::REGION) * 4 + meltab;
+    const int meltab = is_mel_kind(a.out_kind) ? ((a.melr_chunks + 2) + (a.melr_chunks + 1) * a.melr_steps) * GeoR::L * 16 : 0;
+    return (GeoR::TAB_FLOATS + (canon_geometry(a) ? 0 : GeoR::WL_FLOATS) + wv * GeoR::REGION) * 4 + meltab;
 }
+// the 16-wave range-fold instance (launchr_c) has no 12-wave fallback: its layout must fit
+static_assert((GeoR::TAB_FLOATS + 16 * GeoR::REGION) * 4 <= kLdsMax, "16-wave stftr blocks (no mel tables) fit LDS");
 
 template <int KIND, int C, int INF, int WV, int VAR = 0, bool DIR = false, bool RG = false>
 static int launchr_k(const StftLaunch& a, hipStream_t s) {
@@ -474,29 +473,16 @@ static int launchr_k(const StftLaunch& a, hipStream_t s) {
         if (v == 3) return launchr_k<KIND, C, INF, WV, 3>(a, s);
     }
 #endif
-    const int lds = ldsr_bytes(a, WV);
-    if (lds > 163840) return -2;
-    auto kern = stftr_kernel<KIND, C, INF, WV, VAR, DIR, RG>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
-        hipSuccess)
-        return -1;
-    if (a.total_frames == 0) return 0;
-    int grid = grid_for(reinterpret_cast<const void*>(kern), 64 * WV, lds, (a.total_frames + WV - 1) / WV, a.grid,
-                        a.grid_share);
-    const uint64_t streams = (uint64_t)grid * WV;
-    const uint64_t fps = (a.total_frames + streams - 1) / streams;
-    grid = (int)((a.total_frames + fps * WV - 1) / (fps * WV));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WV), lds, s, a, fps);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launch_streams(stftr_kernel<KIND, C, INF, WV, VAR, DIR, RG>, 64 * WV, ldsr_bytes(a, WV), WV, a, s);
 }
 
 // the spectrum kinds always fit 12 regions (125 KiB); the mel kinds fall back to 8 when their
 // tables leave no room
 template <int KIND, int C, int INF, bool DIR = false>
 static int launchr_w(const StftLaunch& a, hipStream_t s) {
-    if constexpr (KIND == OUT_MEL || KIND == OUT_MEL_AMP_DB) {
+    if constexpr (is_mel_kind(KIND)) {
         if (a.melr_chunks <= 0) return -2;
-        if (ldsr_bytes(a, 12) > 163840) return launchr_k<KIND, C, INF, 8, 0, DIR>(a, s);
+        if (ldsr_bytes(a, 12) > kLdsMax) return launchr_k<KIND, C, INF, 8, 0, DIR>(a, s);
     }
     return launchr_k<KIND, C, INF, 12, 0, DIR>(a, s);
 }
@@ -519,22 +505,30 @@ static int launchr_c(const StftLaunch& a, hipStream_t s) {
     }
 }
 
-bool stftr_supports(int n_fft, int win, int hop, int in_format, int channels) {
-    if (n_fft != 2048 || !(channels == 1 || channels == 2)) return false;
-    if (win == n_fft && hop * 4 == n_fft) return in_format == IN_F32 || in_format == IN_S16;
-    // any other geometry (DIR): even win <= n_fft (the frame start t hop - n_fft / 2 is the
-    // reference's t hop - win / 2 - pad_left, lib.rs:400-401), f32
-    return in_format == IN_F32 && hop >= 1 && win >= 2 && win <= n_fft && win % 2 == 0;
-}
+bool stftr_supports(const StftLaunch& a) { return a.n_fft == 2048 && ref_stream_geometry(a); }
 
 int stftr_lds_bytes(const StftLaunch& a) { return ldsr_bytes(a, 8); }
 
 int launch_stftr(const StftLaunch& a, hipStream_t s) {
-    if (!stftr_supports(a.n_fft, a.win, a.hop, a.in_format, a.channels)) return -2;
-    if (!r_canon(a))  // the viewer's geometries: f32 mono / stereo (MultiTrack's mono pool)
-        return a.channels == 2 ? launchr_c<2, IN_F32, true>(a, s) : launchr_c<1, IN_F32, true>(a, s);
-    if (a.in_format == IN_S16) return a.channels == 2 ? launchr_c<2, IN_S16>(a, s) : launchr_c<1, IN_S16>(a, s);
-    return a.channels == 2 ? launchr_c<2, IN_F32>(a, s) : launchr_c<1, IN_F32>(a, s);
+    if (!stftr_supports(a)) return -2;
+    if (!canon_geometry(a))  // the viewer's geometries: f32 mono / stereo (MultiTrack's mono pool)
+        return for_channels_format<true>(a, [&](auto c, auto inf) {
+            return launchr_c<decltype(c)::value, decltype(inf)::value, true>(a, s);
+        });
+    return for_channels_format(a, [&](auto c, auto inf) {
+        return launchr_c<decltype(c)::value, decltype(inf)::value>(a, s);
+    });
+}
+
+// batch kernel 7: stftr at n_fft 2048 (mel kinds need its packed stream), stftq at 256 / 512 / 1024
+static bool stft7_is_r(const StftLaunch& a) { return a.n_fft == 2048; }
+bool stft7_supports(const StftLaunch& a) {
+    if (!stft7_is_r(a)) return stftq_supports(a);
+    return stftr_supports(a) && (!is_mel_kind(a.out_kind) || a.melr_chunks > 0);
+}
+int stft7_lds_bytes(const StftLaunch& a) { return stft7_is_r(a) ? stftr_lds_bytes(a) : stftq_lds_bytes(a); }
+int launch_stft7(const StftLaunch& a, hipStream_t s) {
+    return stft7_is_r(a) ? launch_stftr(a, s) : launch_stftq(a, s);
 }
 
 }  // namespace thesia

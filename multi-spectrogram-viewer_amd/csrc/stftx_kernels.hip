@@ -322,7 +322,7 @@ int launch_irfftx(const float* in, uint64_t n_frames, int length, const int* xpo
     if (length < 2 || (length & (length - 1))) return -2;
     const int NC = length / 2;
     const int lds = kXWaves * ((NC + 3) & ~3) * 8;
-    if (lds > 163840) return -2;
+    if (lds > kLdsMax) return -2;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(irfftx_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
         return -1;
@@ -346,8 +346,8 @@ int launch_stftx(const StftLaunch& a, hipStream_t s) {
     if (a.n_fft < 2 || (a.n_fft & (a.n_fft - 1))) return -2;
     // a separate |X| row only for the mel kinds at n_fft 4096: otherwise a frame's wave takes
     // 8 KiB at n_fft 2048 (16 waves per CU instead of 12)
-    const int lds = stftx_lds_bytes(a.n_fft, a.out_kind == OUT_MEL || a.out_kind == OUT_MEL_AMP_DB);
-    if (lds > 163840) return -2;
+    const int lds = stftx_lds_bytes(a.n_fft, is_mel_kind(a.out_kind));
+    if (lds > kLdsMax) return -2;
     auto kern = a.in_format == IN_S16 ? stftx_kernel<IN_S16> : stftx_kernel<IN_F32>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                             hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)

@@ -208,7 +208,9 @@ class Batch:
 
     @property
     def kernel(self) -> int:
-        """1 stft_kernel, 2 stft2_kernel, 3 stft3_kernel (streaming)."""
+        """The kernel the batch runs: 1 stft_kernel, 2 stft2_kernel, 3 stft3_kernel (streaming),
+        5 stft5_kernel (streaming, n_fft 2048), 7 stftr_kernel / stftq_kernel (streaming, the
+        reference's operation order), 9 stftx_kernel (the reference's operation order)."""
         k = C.c_int()
         check(lib.thesia_batch_kernel(self.handle, C.byref(k)))
         return k.value

@@ -259,7 +259,7 @@ def test_e2e_rgb_multitrack_samples(scale, fast):
 def test_e2e_rgb_multitrack_fast_stft5(scale):
     """MultiTrack's fast path where it takes stft5: one add_tracks of 16
     48 kHz tracks x 250 s (25 000 frames each, 400 000 frames in the call's batch: the automatic
-    rule's kView5MinFrames, engine.hpp), mel and linear rows, images vs the oracle pipeline under
+    rule's kView5MinFrames, engine.cpp), mel and linear rows, images vs the oracle pipeline under
     the same contract as the excerpts, plus the dB rows themselves."""
     from thesia import engine
     sr, n, k = 48000, 250 * 48000, 16
@@ -267,7 +267,7 @@ def test_e2e_rgb_multitrack_fast_stft5(scale):
     win, hop, n_fft = O.track_params(sr)
     T = O.stft_n_frames(n, win, hop)
     assert k * T >= 400000
-    # the automatic rule MultiTrack's fast path applies to this batch (Batch::auto_kernel)
+    # the automatic rule MultiTrack's fast path applies to this batch (auto_kernel, engine.cpp)
     kind = engine.OUT_MEL_AMP_DB if scale == thesia.FreqScale.Mel else engine.OUT_AMP_DB
     plan = engine.Plan(n_fft, win, hop, kind, sr=sr,
                        **({"mel_fb": O.calc_mel_fb_default(sr, n_fft)} if kind == engine.OUT_MEL_AMP_DB else {}))

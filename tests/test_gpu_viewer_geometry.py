@@ -96,7 +96,7 @@ _KINDS = [engine.OUT_MAG, engine.OUT_POWER, engine.OUT_AMP_DB, engine.OUT_POWER_
 def _auto(n_fft, hop, frames=0):
     """The automatic kernel for the mel / linear kinds: stft5 (its viewer column rule,
     stft5_kernels.hip HQ 7) at the 48 kHz geometry for batches of >= 400 000 frames
-    (Batch::kView5MinFrames), stft3 otherwise -- these tests' batches are small."""
+    (kView5MinFrames, engine.cpp), stft3 otherwise -- these tests' batches are small."""
     return 5 if (n_fft, hop) == (2048, 480) and frames >= 400000 else 3
 
 
