@@ -628,7 +628,8 @@ static int build_melp(Plan* p, int S, Plan::Melp& out, int L = 32, int region = 
             best_k0 = k0;
         }
     }
-    // tables: meta rows r = 0 .. C + 1 ({woff(r-1), keep(r-1), xoff(r), 0}); weight rows of
+    // tables: meta rows r = 0 .. C + 1 ({woff(r-1), keep(r-1), xoff(r), xoff(r+1)}: the second
+    // offset lets stft5 issue a chunk's |X| reads two chunks after its meta row); weight rows of
     // chunks 0 .. C (chunk C: the pipeline's read-ahead padding, zero weights)
     std::fill(offs.begin(), offs.end(), -1L);
     std::vector<int> woff((size_t)(C + 1) * L), keep((size_t)(C + 1) * L, -1);
@@ -668,7 +669,8 @@ static int build_melp(Plan* p, int S, Plan::Melp& out, int L = 32, int region = 
         for (int j = 0; j < L; ++j) {
             const int c = r - 1;
             meta[(size_t)r * L + j] = int4{c >= 0 ? woff[(size_t)c * L + j] : 0, c >= 0 ? keep[(size_t)c * L + j] : -1,
-                                           r <= C ? xoff[(size_t)r * L + j] : 0, 0};
+                                           r <= C ? xoff[(size_t)r * L + j] : 0,
+                                           r + 1 <= C ? xoff[(size_t)(r + 1) * L + j] : 0};
         }
     int rc = out.meta.upload(meta.data(), meta.size() * sizeof(int4));
     if (!rc) rc = out.wt.upload(wt.data(), wt.size() * sizeof(float));

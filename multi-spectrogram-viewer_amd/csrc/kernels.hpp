@@ -75,8 +75,9 @@ struct StftLaunch {
     // byte xoff(c) of the stream's LDS region; after its fma chain the running sum is stored
     // at byte woff(c) of the region (the mel's slot behind the |X| row, kMelpOut, or a dummy
     // slot) and ANDed with keep(c) (0: the chunk ends a filter, the next starts from +0).
-    // melp_meta[(c + 1) * L + j] = {woff(c), keep(c), xoff(c + 1), 0}, c = -1 .. melp_chunks - 1
-    // (one zero chunk of padding at the end: the pipeline reads one chunk ahead).
+    // melp_meta[(c + 1) * L + j] = {woff(c), keep(c), xoff(c + 1), xoff(c + 2)}, c = -1 ..
+    // melp_chunks - 1 (offsets past the last chunk are 0; one zero chunk of padding at the end:
+    // the pipelines read ahead, stft5's two chunks with the chunk index clamped to the padding).
     int melp_chunks = 0;
     int melp_steps = 0;
     int melp_v4 = 0;  // n_mels % 4 == 0 and 16-byte aligned rows: float4 row stores

@@ -18,8 +18,15 @@
 //   Lane 0 (A = B = 0) pairs its own outputs differently (O with O, E with E, E[0] and E[8]
 //   with themselves: bins 0, NC and NC/2); per-slot selects cover it, as in stft3.
 //
-// Occupancy: two waves per SIMD (8-wave blocks, 253 VGPRs: the ring, the frame's points, the
-// prefetched hop and the per-lane untangle rotations). Three waves (12-wave blocks, <= 168
+// The mel kinds then run the packed mel stream (melp5) over the frame's |X| row in LDS, its
+// reads two chunks ahead of the fma chain and every |X| offset known two chunks before its
+// reads, so the stream waits for no LDS round trip per chunk. Running the next frame's head
+// (ring shift, prefetch issue, first radix-4 level) inside that stream does not fit the
+// register budget: every form tried spilled.
+//
+// Occupancy: two waves per SIMD (8-wave blocks, 249 VGPRs in the stereo f32 mel instance: the
+// ring, the frame's points, the prefetched hop and the per-lane untangle rotations; no scratch
+// in any instance). Three waves (12-wave blocks, <= 168
 // VGPRs) compiled without spills only with the hop prefetched by LDS-DMA, the rotations in LDS
 // and 32-bit frame words, and measured slower; those compile-time variants (and
 // the unfused window / split partner-row reads) were removed from this file in round 3 and live
@@ -135,14 +142,18 @@ __device__ __forceinline__ void untangle5(const float2 (&v)[32], bool lane0, con
 }
 
 // The packed mel stream (engine.cpp build_melp, kernels.hpp melp_*): the chunks of the lane's
-// filters back to back, software-pipelined one chunk ahead (chunk c + 1's meta, weight and |X|
-// reads are issued before chunk c's fma chain; chunk c + 1's |X| offset came with chunk c's
-// meta). A chunk ends by storing its running sum at woff(c) of the region (the mel's slot, or a
-// dummy slot while the filter continues) and ANDing it with keep(c): +0 after a filter's last
-// chunk. The chain of each mel is mel4's k-ascending fma chain (identical bits). The frame's
-// mels then leave as dB rows: one 16-byte store per lane for n_mels % 4 == 0.
+// filters back to back, software-pipelined two chunks ahead (chunk c + 2's meta, weight and |X|
+// reads are issued before chunk c's fma chain). A chunk's |X| offset comes with the meta of the
+// chunk two before it, so no issue of reads waits for the reads of the issue before it; reads
+// past the last chunk clamp to the tables' zero padding chunk (read, not used). A chunk ends by
+// storing its running sum at woff(c) of the region (the mel's slot, or a dummy slot while the
+// filter continues) and ANDing it with keep(c): +0 after a filter's last chunk. The chain of
+// each mel is mel4's k-ascending fma chain (identical bits). The frame's mels then leave as dB
+// rows: one 16-byte store per lane for n_mels % 4 == 0.
+// D = 0 (experiment builds only, for A/B): one chunk ahead with chunk c + 1's offset taken from
+// chunk c's meta, every issue waiting for the meta read of the one before.
 static_assert(Geo5::RS == kStft5Region && Geo2<Geo5::NC>::F4 == kMelpOut, "melp region layout");
-template <int S>
+template <int S, int D>
 __device__ __forceinline__ void melp5(const StftLaunch& a, float* region, const int4* meta,
                                       const float4* wt, int j, uint64_t g, bool valid) {
     constexpr int L = Geo5::L;
@@ -159,6 +170,7 @@ __device__ __forceinline__ void melp5(const StftLaunch& a, float* region, const 
         int4 m;
     };
     auto issue = [&](int c, int xoff, Buf& b) {
+        if constexpr (D > 0) c = c < C ? c : C;
         b.m = mp[(c + 1) * L];
 #pragma unroll
         for (int u = 0; u < S; ++u) b.w[u] = wp[(c * S + u) * L];
@@ -180,22 +192,43 @@ __device__ __forceinline__ void melp5(const StftLaunch& a, float* region, const 
         *reinterpret_cast<float*>(rb + b.m.x) = acc;
         acc = __builtin_bit_cast(float, __builtin_bit_cast(int, acc) & b.m.y);
     };
-    Buf A, B;
-    int c = 0;
-    const int x0 = mp[0].z;
-    if (C & 1) {
-        issue(0, x0, B);
-        issue(1, B.m.z, A);
-        chain(B);
-        c = 1;
+    if constexpr (D == 0) {
+        Buf A, B;
+        int c = 0;
+        const int x0 = mp[0].z;
+        if (C & 1) {
+            issue(0, x0, B);
+            issue(1, B.m.z, A);
+            chain(B);
+            c = 1;
+        } else {
+            issue(0, x0, A);
+        }
+        for (; c < C; c += 2) {  // C - c even; chunk C is the tables' zero padding (read, not used)
+            issue(c + 1, A.m.z, B);
+            chain(A);
+            issue(c + 2, B.m.z, A);
+            chain(B);
+        }
     } else {
-        issue(0, x0, A);
-    }
-    for (; c < C; c += 2) {  // C - c even; chunk C is the tables' zero padding (read, not used)
-        issue(c + 1, A.m.z, B);
-        chain(A);
-        issue(c + 2, B.m.z, A);
-        chain(B);
+        static_assert(D == 2, "pipeline depth");
+        Buf B0, B1, B2;  // chunks c, c + 1, c + 2 (mod 3)
+        const int4 m0 = mp[0];
+        issue(0, m0.z, B0);
+        issue(1, m0.w, B1);
+        int c = 0;
+        for (; c + 3 <= C; c += 3) {
+            issue(c + 2, B0.m.w, B2);
+            chain(B0);
+            issue(c + 3, B1.m.w, B0);
+            chain(B1);
+            issue(c + 4, B2.m.w, B1);
+            chain(B2);
+        }
+        // after the rounds of three, B0 holds chunk c and B1 chunk c + 1 (both issued): the one
+        // or two chunks left when C is no multiple of 3
+        if (c < C) chain(B0);
+        if (c + 1 < C) chain(B1);
     }
     wave_lds_sync();
     const int n_mels = a.n_mels;
@@ -251,6 +284,8 @@ stft5_kernel(StftLaunch a, uint64_t fps, int rs) {
     constexpr int NPRE = VIEW ? HQ + 1 : SH;  // rows prefetched per frame
     constexpr int KEEP = P - NPRE;            // ring rows carried into the next frame
     static_assert(KEEP > 0, "hop shorter than the frame");
+    // the packed mel stream's read-ahead; VAR bit 1 (experiment): the chained one-chunk stream
+    constexpr int kDepth = (VAR & 2) ? 0 : 2;
 
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int kTab = G::TAB_FLOATS + (kRot ? 3 * G::TW_FLOATS : 0);
@@ -586,8 +621,8 @@ stft5_kernel(StftLaunch a, uint64_t fps, int rs) {
             wave_lds_sync();
             MARK5(untangled, 6);
             if (packed) {
-                if (a.melp_steps == 2) melp5<2>(a, region, pm_lds, pw_lds, j, g, valid);
-                else melp5<3>(a, region, pm_lds, pw_lds, j, g, valid);
+                if (a.melp_steps == 2) melp5<2, kDepth>(a, region, pm_lds, pw_lds, j, g, valid);
+                else melp5<3, kDepth>(a, region, pm_lds, pw_lds, j, g, valid);
             }
 #ifndef THESIA_MELP_ONLY
             else if (a.mel_chunks == 8) mel4p<NC, 8>(a, region, mel_lds, xo_lds, j, g, valid);
@@ -683,6 +718,9 @@ static int launch5_k(const StftLaunch& a, hipStream_t stream) {
     if constexpr (VAR == 0 && C == 2 && INF == IN_F32) {
         const char* e = getenv("THESIA_STFT_VARIANT");
         if (e && atoi(e) == 1) return launch5_k<OK, C, INF, 1>(a, stream);  // phase ring
+        if constexpr (OK == 2) {  // the mel stream as it was: one chunk ahead, the offsets chained
+            if (e && atoi(e) == 2) return launch5_k<OK, C, INF, 2>(a, stream);
+        }
     }
 #endif
     const int rs = region_stride5<OK, VAR>(a);
