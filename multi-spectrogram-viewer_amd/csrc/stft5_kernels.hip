@@ -24,9 +24,17 @@
 // (ring shift, prefetch issue, first radix-4 level) inside that stream does not fit the
 // register budget: every form tried spilled.
 //
-// Occupancy: two waves per SIMD (8-wave blocks, 249 VGPRs in the stereo f32 mel instance: the
-// ring, the frame's points, the prefetched hop and the per-lane untangle rotations; no scratch
-// in any instance). Three waves (12-wave blocks, <= 168
+// The frame loop's LDS reads are issued ahead of their use, so that fewer round trips are
+// waited for with nothing else to do (profiles/r08_stft5_round_trips): half of the
+// window row before the ring insert; the stage-1 twiddles in rolling batches of 4, the first
+// before the last DFT-8; and in the transposes both rows of a component read at once, the im
+// writes going out behind the re reads (two round trips per frame pair instead of four). The
+// rows are bit-identical to the serial forms'. Holding a frame's mel row store until the next
+// frame's loads are out measured slower and is not in this file.
+//
+// Occupancy: two waves per SIMD (8-wave blocks, 255 VGPRs in the stereo f32 mel instance: the
+// ring, the frame's points, the prefetched hop, the per-lane untangle rotations and the reads
+// in flight; no scratch in any instance). Three waves (12-wave blocks, <= 168
 // VGPRs) compiled without spills only with the hop prefetched by LDS-DMA, the rotations in LDS
 // and 32-bit frame words, and measured slower; those compile-time variants (and
 // the unfused window / split partner-row reads) were removed from this file in round 3 and live
@@ -286,6 +294,13 @@ stft5_kernel(StftLaunch a, uint64_t fps, int rs) {
     static_assert(KEEP > 0, "hop shorter than the frame");
     // the packed mel stream's read-ahead; VAR bit 1 (experiment): the chained one-chunk stream
     constexpr int kDepth = (VAR & 2) ? 0 : 2;
+    // VAR bits 2, 4, 5 (experiment): the frame loop's LDS reads as they were -- bit 2 the four
+    // serial transpose round trips, bit 4 the whole window row read after the ring insert, bit 5
+    // the stage-1 twiddles in two batches of 8 after the DFT-32. The phase ring keeps all three
+    // (it has no registers left for the other forms).
+    constexpr bool kT4 = (VAR & 4) != 0 || kRot;
+    constexpr bool kWinEarly = (VAR & 16) == 0 && !kRot;
+    constexpr bool kTwRoll = (VAR & 32) == 0 && !kRot;
 
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int kTab = G::TAB_FLOATS + (kRot ? 3 * G::TW_FLOATS : 0);
@@ -396,6 +411,19 @@ stft5_kernel(StftLaunch a, uint64_t fps, int rs) {
             wc = jc;
             asm volatile("" : "+v"(wc));
         }
+        // the window words of the first NWE of the four butterfly pairs (8 float4 of the row's
+        // 16) are read here, ahead of the ring shift and the wait for the prefetched hop; all 16
+        // do not fit (48 bytes of scratch in the stereo f32 mel instance)
+        constexpr int NWE = kWinEarly ? 2 : 0;
+        float4 wall[kWinEarly ? 4 * NWE : 1];
+        if constexpr (kWinEarly) {
+            const float4* wr0 = reinterpret_cast<const float4*>(wtl + wc * G::WL_STRIDE);
+            static_for<0, 4 * NWE>([&](auto ic) {
+                constexpr int i = decltype(ic)::value;
+                wall[i] = wr0[4 * (i % 4) + i / 4];
+            });
+            __builtin_amdgcn_sched_barrier(0);
+        }
         // ---- the frame's raw samples: shift by SH points + the prefetched hop ----
         if (pre_ok && kRot) {
             // the oldest group takes the new hop; the ring's origin moves one group on
@@ -476,7 +504,12 @@ stft5_kernel(StftLaunch a, uint64_t fps, int rs) {
         {
         static_for<0, 4>([&](auto jc) {
             constexpr int jp = decltype(jc)::value;
-            const float4 wq[4] = {wg[0][jp], wg[1][jp], wg[2][jp], wg[3][jp]};
+            float4 wq[4];
+            if constexpr (jp < NWE) {
+                wq[0] = wall[4 * jp]; wq[1] = wall[4 * jp + 1]; wq[2] = wall[4 * jp + 2]; wq[3] = wall[4 * jp + 3];
+            } else {
+                wq[0] = wg[0][jp]; wq[1] = wg[1][jp]; wq[2] = wg[2][jp]; wq[3] = wg[3][jp];
+            }
             static_for<0, 2>([&](auto hc) {
                 constexpr int h = decltype(hc)::value, jj = 2 * jp + h;
                 auto wv = [&](int t) {
@@ -501,11 +534,48 @@ stft5_kernel(StftLaunch a, uint64_t fps, int rs) {
         dif_fft<8, 1, 0, P>(v);
         dif_fft<8, 1, 8, P>(v);
         dif_fft<8, 1, 16, P>(v);
+        const float4* tp = reinterpret_cast<const float4*>(twtab) + wc + phs * (P / 2 * L);
+        // stage-1 twiddles in rolling batches of 4 float4 (two k1 each): batch 0 is read before the
+        // last DFT-8, batch b + 1 before batch b's products, so no read is waited for right
+        // after its issue (batches of 8 in this shape do not fit: scratch)
+        float4 twa[kTwRoll ? 4 : 1], twb[kTwRoll ? 4 : 1];
+        auto tw_rd = [&](float4* t, auto bc) {
+            static_for<0, 4>([&](auto uc) { t[decltype(uc)::value] = tp[(4 * decltype(bc)::value + decltype(uc)::value) * L]; });
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        auto tw_mul = [&](const float4* t, auto bc) {
+            static_for<0, 4>([&](auto uc) {
+                constexpr int u = decltype(uc)::value, q = 4 * decltype(bc)::value + u;
+                if constexpr (q > 0) {
+                    constexpr int pk0 = ce_pos(P, 2 * q);
+                    v[pk0] = cmul(v[pk0], make_float2(t[u].x, t[u].y));
+                }
+                constexpr int pk1 = ce_pos(P, 2 * q + 1);
+                v[pk1] = cmul(v[pk1], make_float2(t[u].z, t[u].w));
+            });
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        constexpr std::integral_constant<int, 0> b0{};
+        constexpr std::integral_constant<int, 1> b1{};
+        constexpr std::integral_constant<int, 2> b2{};
+        constexpr std::integral_constant<int, 3> b3{};
+        if constexpr (kTwRoll) {
+            __builtin_amdgcn_sched_barrier(0);
+            tw_rd(twa, b0);
+        }
         dif_fft<8, 1, 24, P>(v);
         pin(v);
         MARK5(stage1, 1);
-        {
-            const float4* tp = reinterpret_cast<const float4*>(twtab) + wc + phs * (P / 2 * L);
+        if constexpr (kTwRoll) {
+            __builtin_amdgcn_sched_barrier(0);
+            tw_rd(twb, b1);
+            tw_mul(twa, b0);
+            tw_rd(twa, b2);
+            tw_mul(twb, b1);
+            tw_rd(twb, b3);
+            tw_mul(twa, b2);
+            tw_mul(twb, b3);
+        } else {
             static_for<0, P / 2 / G::TWC>([&](auto cc) {
                 constexpr int c0 = decltype(cc)::value * G::TWC;
                 __builtin_amdgcn_sched_barrier(0);
@@ -525,39 +595,81 @@ stft5_kernel(StftLaunch a, uint64_t fps, int rs) {
         MARK5(twiddled, 2);
         // ---- transpose (re, then im): rows A = j and B = 32 - j, first radix-2 step ----
         // v[n] <- A[n] + A[n + 16]; v[16 + n] <- B[n] - B[n + 16] (n < 16)
+        if constexpr (kT4) {  // experiment: four serial round trips (each row read waited for)
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            wave_lds_sync();
-            static_for<0, P>([&](auto kc) {
-                constexpr int k1 = decltype(kc)::value;
-                constexpr int pk = ce_pos(P, k1);
-                region[k1 * S + wc] = e == 0 ? v[pk].x : v[pk].y;
-            });
-            wave_lds_sync();
-            // row A lands in the component just written out: A[n] into v[n].e (e = re / im;
-            // explicit branches on the unrolled e: a reference select would put v in scratch)
+            for (int e = 0; e < 2; ++e) {
+                wave_lds_sync();
+                static_for<0, P>([&](auto kc) {
+                    constexpr int k1 = decltype(kc)::value;
+                    constexpr int pk = ce_pos(P, k1);
+                    region[k1 * S + wc] = e == 0 ? v[pk].x : v[pk].y;
+                });
+                wave_lds_sync();
+                // row A lands in the component just written out: A[n] into v[n].e (e = re / im;
+                // explicit branches on the unrolled e: a reference select would put v in scratch)
+                const float4* ra = static_cast<const float4*>(__builtin_assume_aligned(region + wj * S, 16));
+                const float4* rb = static_cast<const float4*>(__builtin_assume_aligned(region + wjb * S, 16));
+                auto put = [&](float2& x, float val) {
+                    if (e == 0) x.x = val; else x.y = val;
+                };
+                auto get = [&](const float2& x) { return e == 0 ? x.x : x.y; };
+                static_for<0, 8>([&](auto qc) {
+                    constexpr int q = decltype(qc)::value;
+                    const float4 t = ra[q];
+                    put(v[4 * q], t.x); put(v[4 * q + 1], t.y); put(v[4 * q + 2], t.z); put(v[4 * q + 3], t.w);
+                });
+                static_for<0, 16>([&](auto nc) {  // even outputs of A: A[n] + A[n + 16]
+                    constexpr int nn = decltype(nc)::value;
+                    put(v[nn], get(v[nn]) + get(v[nn + 16]));
+                });
+                // row B: v[16 + n].e = B[n] - B[n + 16]
+                {
+                    float4 xb[8];
+                    static_for<0, 4>([&](auto qc) {
+                        constexpr int q = decltype(qc)::value;
+                        xb[q] = rb[q];
+                        xb[4 + q] = rb[q + 4];
+                    });
+                    static_for<0, 4>([&](auto uc) {
+                        constexpr int u = decltype(uc)::value, n0 = 4 * u;
+                        put(v[16 + n0], xb[u].x - xb[u + 4].x);
+                        put(v[17 + n0], xb[u].y - xb[u + 4].y);
+                        put(v[18 + n0], xb[u].z - xb[u + 4].z);
+                        put(v[19 + n0], xb[u].w - xb[u + 4].w);
+                    });
+                }
+            }
+        } else {
+            // Two LDS round trips per frame pair instead of four. A wave's LDS instructions
+            // execute in order, so the im writes go out behind the re reads without waiting for
+            // them and are hidden under their return; a component's two rows land in 64
+            // registers (its 32 of v are dead once written out) and only then are combined.
             const float4* ra = static_cast<const float4*>(__builtin_assume_aligned(region + wj * S, 16));
             const float4* rb = static_cast<const float4*>(__builtin_assume_aligned(region + wjb * S, 16));
-            auto put = [&](float2& x, float val) {
-                if (e == 0) x.x = val; else x.y = val;
+            float4 xa[8], xb[8];
+            auto wr = [&](auto ec) {
+                static_for<0, P>([&](auto kc) {
+                    constexpr int k1 = decltype(kc)::value;
+                    constexpr int pk = ce_pos(P, k1);
+                    region[k1 * S + wc] = decltype(ec)::value == 0 ? v[pk].x : v[pk].y;
+                });
             };
-            auto get = [&](const float2& x) { return e == 0 ? x.x : x.y; };
-            static_for<0, 8>([&](auto qc) {
-                constexpr int q = decltype(qc)::value;
-                const float4 t = ra[q];
-                put(v[4 * q], t.x); put(v[4 * q + 1], t.y); put(v[4 * q + 2], t.z); put(v[4 * q + 3], t.w);
-            });
-            static_for<0, 16>([&](auto nc) {  // even outputs of A: A[n] + A[n + 16]
-                constexpr int nn = decltype(nc)::value;
-                put(v[nn], get(v[nn]) + get(v[nn + 16]));
-            });
-            // row B: v[16 + n].e = B[n] - B[n + 16]
-            {
-                float4 xb[8];
-                static_for<0, 4>([&](auto qc) {
-                    constexpr int q = decltype(qc)::value;
-                    xb[q] = rb[q];
-                    xb[4 + q] = rb[q + 4];
+            auto rd = [&]() {
+                static_for<0, 8>([&](auto qc) { xa[decltype(qc)::value] = ra[decltype(qc)::value]; });
+                static_for<0, 8>([&](auto qc) { xb[decltype(qc)::value] = rb[decltype(qc)::value]; });
+            };
+            // the same adds on the same operands as the serial form: A[n] + A[n + 16] into
+            // v[n].e, B[n] - B[n + 16] into v[16 + n].e
+            auto comb = [&](auto ec) {
+                auto put = [&](float2& x, float val) {
+                    if (decltype(ec)::value == 0) x.x = val; else x.y = val;
+                };
+                static_for<0, 4>([&](auto uc) {
+                    constexpr int u = decltype(uc)::value, n0 = 4 * u;
+                    put(v[n0], xa[u].x + xa[u + 4].x);
+                    put(v[n0 + 1], xa[u].y + xa[u + 4].y);
+                    put(v[n0 + 2], xa[u].z + xa[u + 4].z);
+                    put(v[n0 + 3], xa[u].w + xa[u + 4].w);
                 });
                 static_for<0, 4>([&](auto uc) {
                     constexpr int u = decltype(uc)::value, n0 = 4 * u;
@@ -566,7 +678,21 @@ stft5_kernel(StftLaunch a, uint64_t fps, int rs) {
                     put(v[18 + n0], xb[u].z - xb[u + 4].z);
                     put(v[19 + n0], xb[u].w - xb[u + 4].w);
                 });
-            }
+            };
+            constexpr std::integral_constant<int, 0> re{};
+            constexpr std::integral_constant<int, 1> im{};
+            wave_lds_sync();
+            wr(re);
+            wave_lds_sync();
+            rd();
+            wave_lds_sync();
+            __builtin_amdgcn_sched_barrier(0);
+            wr(im);
+            wave_lds_sync();
+            __builtin_amdgcn_sched_barrier(0);
+            comb(re);
+            rd();
+            comb(im);
         }
         wave_lds_sync();
         MARK5(transposed, 3);
@@ -720,6 +846,11 @@ static int launch5_k(const StftLaunch& a, hipStream_t stream) {
         if (e && atoi(e) == 1) return launch5_k<OK, C, INF, 1>(a, stream);  // phase ring
         if constexpr (OK == 2) {  // the mel stream as it was: one chunk ahead, the offsets chained
             if (e && atoi(e) == 2) return launch5_k<OK, C, INF, 2>(a, stream);
+            // the frame loop's LDS reads as they were, and each of the three changes alone
+            if (e && atoi(e) == 3) return launch5_k<OK, C, INF, 4 | 16 | 32>(a, stream);
+            if (e && atoi(e) == 4) return launch5_k<OK, C, INF, 16 | 32>(a, stream);  // transposes
+            if (e && atoi(e) == 5) return launch5_k<OK, C, INF, 4 | 16>(a, stream);   // twiddles
+            if (e && atoi(e) == 6) return launch5_k<OK, C, INF, 4 | 32>(a, stream);   // window
         }
     }
 #endif
